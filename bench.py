@@ -1,7 +1,14 @@
 """Benchmark: RF Msamples/s and fields/s of the MI355X decode path (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     (N > 1: torch.distributed.run, one rank per GPU: one capture field-sharded, strong scaling)
+
+A plain run sets up, warms up, times the K steps and prints the result line (the
+headline figure and the decoder's own counters).  --dump-outputs DIR also writes
+what the last timed step decoded as DIR/<name>.npy (dump_outputs below).  --full
+adds everything that takes work of its own: HIP-event profiling of the timed steps'
+kernels, the demod's isolated roofline leg, the sharded workload's same-share
+single-GPU leg and the CPU baseline (the oracle on the host cores).
 
 N = 1 (default; BASELINE.json configs[1]): 60 s of synthetic NTSC CAV RF,
 40 MSPS, 8-bit, synthesised on the GPU straight into HBM (same signal model as
@@ -86,7 +93,14 @@ def parse():
                     help='oracle baseline sample: frames per process (SURVEY §8(d): a 60-frame prefix)')
     ap.add_argument('--cpu-procs', type=int, default=0,
                     help='processes of the multi-process CPU baseline (default: the CPUs visible, at most 16)')
-    ap.add_argument('--no-cpu', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also: HIP-event profiling of the timed steps (kernels_ms, the demod spans), the '
+                         "demod's isolated roofline leg, the same-share single-GPU leg (sharded, N > 1) and "
+                         'the CPU baseline; a plain run times the steps and prints the headline only')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the last step decoded to DIR/<name>.npy '
+                         '(float32 / float64, under 64 MB; see dump_outputs)')
+    ap.add_argument('--no-cpu', action='store_true', help='--full without the CPU baseline')
     ap.add_argument('--no-comb', action='store_true', help='stop at .tbc (skip the 2D comb stage)')
     ap.add_argument('--host-io', action='store_true',
                     help='PCIe-inclusive (not the headline): each step hands the capture over from host memory '
@@ -97,9 +111,11 @@ def parse():
                          'from there through the HBM ring (ldg_stream_open, 2 GiB; lddecode.py\'s path minus the '
                          'output writes), frames and rgb48 left in HBM; NTSC, one rank or --independent')
     ap.add_argument('--prof-all', action='store_true',
-                    help='HIP-event timing of every kernel (default: the demod only, the roofline kernel)')
+                    help='--full: HIP-event timing of every kernel (default: the demod only, the roofline kernel)')
     args = ap.parse_args()
     world = int(os.environ.get('WORLD_SIZE', '1'))
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps at least 1, --warmup at least 0')
     if (args.stream_file or args.host_io) and (args.system == 'PAL' or args.sharded or
                                                (world > 1 and not args.independent)):
         ap.error('--stream-file / --host-io: the NTSC capture workload (one rank, or --independent)')
@@ -269,6 +285,88 @@ def demod_issue_lag(tab):
             'median_gap_ms': round(float(np.median(gap)), 4),
             'note': 'timed steps\' demod launches, issue order; gap = start - latest earlier end, late = host issue '
                     '(steady clock mapped onto the device clock) - that end; host-late: gap > 5 us and late > 0'}
+
+
+DUMP_FRAMES = 4               # the last frames of the last timed step that --dump-outputs writes in full
+
+
+def last_frames(dec, nframes):
+    """(top slot, bottom slot, top start, bottom start, top lines, bottom lines) of the last `nframes` frames the last
+    decode completed, oldest first: its field reads are still in the read cache, and each one
+    starts where the one before it ends (start + nextfieldoffset, lddecode_core.py:1204), so
+    the chain is walked backwards from the decode's final position.  Where two cached reads
+    end at the same sample (a read decoded again at another MTF level), the lower level is
+    taken: the choice depends on the decode alone, not on launch timing."""
+    from ldgpu import native
+    if not dec.last_meta:
+        return []
+    ends = {}
+    for (start, mtf), (slot, info) in dec.cache.items():
+        if info.status == native.FS_VALID:
+            k = start + info.nextfieldoffset
+            if k not in ends or mtf < ends[k][1]:
+                ends[k] = (start, mtf, slot, bool(info.istop), int(info.linecount))
+    fields, pos = [], int(dec.last_meta['nextsample'])
+    while len(fields) < 2 * nframes and pos in ends:
+        fields.append(ends[pos])
+        pos = ends[pos][0]
+    fields.reverse()
+    fields = fields[len(fields) % 2:]
+    out = []
+    for a, b in zip(fields[0::2], fields[1::2]):
+        top, bot = (a, b) if a[3] else (b, a)
+        out.append((top[2], bot[2], top[0], bot[0], top[4], bot[4]))
+    return out
+
+
+def dump_outputs(path, dec, rank, world, comb):
+    """--dump-outputs: what the last timed step decoded, as float32 / float64 .npy files
+    (about 40 MB).  A step leaves its frames in HBM and hands its caller the frame count,
+    the picture numbers and the final position; the decoded fields stay in the context's
+    read slots until the next decode.  Written from those, before anything else runs:
+      summary          [frames decoded, final capture position, 48 kHz audio samples]   float64
+      frame_numbers    the VBI picture number of every frame of the step (NaN: none)    float64
+      frame_starts     [top, bottom] field read start of each of the last DUMP_FRAMES frames
+      tbc_frames       those frames as the step assembles them (ldg_assemble_frames over the
+                       step's own field slots), outlinelen x frame_lines each           float32
+      field_linelocs   the final line locations of their fields, top then bottom        float64
+      comb_burst_ema   the burst-level EMA per line of the step's last comb launch, and
+      comb_state       the EMA it carried out of the step (NTSC comb only)              float64
+      rgb48_frames     the comb's rgb48 of tbc_frames, as one comb process that starts at the
+                       first of them (so NTSC's burst EMA starts fresh there)           float32
+    Ranks after the first prefix their files with rank<k>_."""
+    os.makedirs(path, exist_ok=True)
+    pre = '' if rank == 0 else 'rank%d_' % rank
+    ctx = dec.ctx
+
+    def put(name, a, dtype):
+        np.save(os.path.join(path, pre + name + '.npy'), np.ascontiguousarray(a, dtype=dtype))
+
+    meta = dec.last_meta or {}
+    put('summary', [len(dec.frame_numbers), meta.get('nextsample', 0), dec.pcm_samples], np.float64)
+    put('frame_numbers', [np.nan if n is None else n for n in dec.frame_numbers], np.float64)
+    if comb and dec.sysp.name == 'NTSC' and dec.frame_numbers:
+        put('comb_burst_ema', ctx.debug(0, 50, np.float64, 1 << 20), np.float64)
+        put('comb_state', ctx.debug(0, 51, np.float64, 1), np.float64)
+    fr = last_frames(dec, DUMP_FRAMES)
+    put('frame_starts', np.array([f[2:4] for f in fr]).reshape(-1, 2), np.float64)
+    if not fr:
+        return
+    W, H = dec.sysp.outlinelen, dec.sysp.frame_lines
+    locs = np.zeros((2 * len(fr), 320))          # each field's own lines (263 NTSC, 313 PAL at most), zero-padded
+    for i, f in enumerate(fr):
+        for j in (0, 1):
+            locs[2 * i + j, :f[4 + j]] = ctx.debug(f[j], 24, np.float64, 1 << 12)[:f[4 + j]]
+    put('field_linelocs', locs, np.float64)
+    pics = ctx.assemble_frames([f[0] for f in fr], [f[1] for f in fr], W, H)
+    put('tbc_frames', pics, np.float32)
+    if comb:
+        if dec.sysp.name == 'PAL':
+            rgb = ctx.comb_pal(pics)
+        else:
+            ctx.comb_reset()
+            rgb = ctx.comb_ntsc(pics)
+        put('rgb48_frames', rgb, np.float32)
 
 
 def progress(rank, what):
@@ -594,7 +692,10 @@ def main():
             torch.cuda.synchronize()
             dist.barrier()
 
-    dec.ctx.profile(True if args.prof_all else 'demod')
+    # HIP-event profiling of the timed steps' kernels: with --full (LDG_SPANTABLE needs it too)
+    profiled = args.full or args.prof_all or bool(os.environ.get('LDG_SPANTABLE'))
+    if profiled:
+        dec.ctx.profile(True if args.prof_all else 'demod')
     reads0, used0 = dec.stats['reads'], dec.stats['reads_used']
     barrier()
     t0 = time.perf_counter()
@@ -610,40 +711,47 @@ def main():
         progress(rank, 'step %d done' % (k + 1))
     barrier()
     dt = time.perf_counter() - t0
-    stats = dec.ctx.profile_stats()
     if dec.htrace is not None:                 # LDG_HOSTTRACE=<file>: the host timeline of the timed steps
         with open(os.environ['LDG_HOSTTRACE'], 'w') as f:
             f.write('# t0_ms %.4f (time.perf_counter() * 1e3 at the timed region\'s start)\n' % (t0 * 1e3))
             for t, ev, n in dec.htrace:
                 if t >= t0:
                     f.write('%.4f %s %d\n' % ((t - t0) * 1e3, ev, n))
-    spans = dec.ctx.profile_spans()        # (launches, total ms) of the demod's execution spans
-    busy = dec.ctx.profile_spans_union()   # (launches, ms with at least one demod executing)
-    span_tab = dec.ctx.profile_span_table()
-    issue = demod_issue_lag(span_tab)
-    if os.environ.get('LDG_SPANTABLE'):        # per-launch (start, end, issue, host issue) for timeline tools
-        np.savetxt(os.environ['LDG_SPANTABLE'], span_tab, fmt='%.4f')
-    dec.ctx.profile(False)
+    stats, spans, busy, issue = {}, None, None, None
+    if profiled:
+        stats = dec.ctx.profile_stats()
+        spans = dec.ctx.profile_spans()        # (launches, total ms) of the demod's execution spans
+        busy = dec.ctx.profile_spans_union()   # (launches, ms with at least one demod executing)
+        span_tab = dec.ctx.profile_span_table()
+        issue = demod_issue_lag(span_tab)
+        if os.environ.get('LDG_SPANTABLE'):    # per-launch (start, end, issue, host issue) for timeline tools
+            np.savetxt(os.environ['LDG_SPANTABLE'], span_tab, fmt='%.4f')
+        dec.ctx.profile(False)
+    if args.dump_outputs:                      # before any other leg touches the step's field slots
+        dump_outputs(args.dump_outputs, dec, rank, world, comb=not args.no_comb)
+        progress(rank, 'outputs written to %s' % args.dump_outputs)
     # the roofline leg: the demod alone (kernel ldg_k_demod_iso) over one full-width launch's
     # reads, ISO_ITERS launches back to back, HIP events on its stream -- the per-dispatch
     # figure a kernel trace of this command reports for ldg_k_demod_iso (profiles/)
-    if hasattr(wl, 'before_iso'):
-        wl.before_iso()
-    if dist is not None and shared_device:
-        # ranks sharing a GPU (a rehearsal on a smaller box) take the leg in turn, so each
-        # times the kernel alone on the device as a one-rank-per-GPU run does
-        for r in range(world):
+    iso = None
+    if args.full:
+        if hasattr(wl, 'before_iso'):
+            wl.before_iso()
+        if dist is not None and shared_device:
+            # ranks sharing a GPU (a rehearsal on a smaller box) take the leg in turn, so each
+            # times the kernel alone on the device as a one-rank-per-GPU run does
+            for r in range(world):
+                barrier()
+                if r == rank:
+                    iso = iso_leg(dec)
             barrier()
-            if r == rank:
-                iso_reads, iso_ms, cut_ms = iso_leg(dec)
-        barrier()
-    else:
-        iso_reads, iso_ms, cut_ms = iso_leg(dec)
+        else:
+            iso = iso_leg(dec)
     reads_timed = dec.stats['reads'] - reads0
     used_timed = dec.stats['reads_used'] - used0
     checks = wl.checks()
     same_share = None
-    if dist is not None and isinstance(wl, ShardedWorkload):
+    if args.full and dist is not None and isinstance(wl, ShardedWorkload):
         # the N = 1 rate of the same per-rank work, rank 0 alone on its GPU (others wait)
         barrier()
         if rank == 0:
@@ -669,6 +777,23 @@ def main():
 
     msps = consumed_all / dt_max / 1e6
     fields_s = 2 * frames_all / dt_max
+    roofline = roofline_of(args, wl, iso, consumed, used_timed, stats, spans, busy) if args.full else None
+    cpu = None
+    if args.full and not args.no_cpu and world == 1:
+        # the capture in host memory, as a loader would read it (the CPU path's input)
+        procs = args.cpu_procs or min(16, len(os.sched_getaffinity(0)))
+        progress(rank, 'CPU baseline (oracle, %d frames per process, 1 and %d processes)' % (args.cpu_frames, procs))
+        cpu = cpu_baseline(wl.host_capture, wl.fmt, wl.system, args.cpu_frames, procs)
+    report(args, wl, dec, world, dt_max, msps, fields_s, frames, step_ms, checks, issue, stats, roofline, cpu,
+           same_share)
+    if dist is not None:
+        dist.destroy_process_group()
+
+
+def roofline_of(args, wl, iso, consumed, used_timed, stats, spans, busy):
+    """--full: the roofline entry of the result line, from the isolated leg's launch times
+    (iso: iso_leg()) and the timed steps' profile (stats, spans, busy)."""
+    iso_reads, iso_ms, cut_ms = iso
     # Roofline of the dominant kernel, the demod (the one kernel that consumes the capture and
     # fills the chip: one 150 KiB-LDS workgroup per CU).  Unit of work = one RF sample consumed;
     # algorithmic bytes per unit = SURVEY §8(d): input (1 B u8, 5/4 .lds, 4/3 .r30, 2 s16) +
@@ -747,18 +872,19 @@ def main():
     if not args.no_comb:
         roofline['bytes_per_sample_with_comb'] = round(bps + (PAL_COMB_BYTES_PER_SAMPLE if pal else
                                                               NTSC_COMB_BYTES_PER_SAMPLE), 4)
-    cpu = None
-    if not args.no_cpu and world == 1:
-        # the capture in host memory, as a loader would read it (the CPU path's input)
-        procs = args.cpu_procs or min(16, len(os.sched_getaffinity(0)))
-        progress(rank, 'CPU baseline (oracle, %d frames per process, 1 and %d processes)' % (args.cpu_frames, procs))
-        cpu = cpu_baseline(wl.host_capture, wl.fmt, wl.system, args.cpu_frames, procs)
+    return roofline
+
+
+def report(args, wl, dec, world, dt_max, msps, fields_s, frames, step_ms, checks, issue, stats, roofline, cpu,
+           same_share):
+    """Print the result line (rank 0).  roofline, kernels_ms, cpu_baseline and checks.demod_issue
+    are filled by --full."""
     line = {
         'metric': 'RF Msamples/s (40 MSPS %s, full RF->.tbc decode)' % args.system, 'value': round(msps, 3),
         'unit': 'RF Msamples/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
         'ms_per_step': round(dt_max / args.steps * 1e3, 3), 'higher_is_better': True, 'scaling': wl.scaling,
         'vs_baseline': None, 'dtype': 'f64', 'data': wl.data, 'config': wl.config(frames),
-        'fields_per_s': round(fields_s, 1), 'realtime_x': round(msps / 40.0, 2),
+        'fields_per_s': round(fields_s, 1), 'realtime_x': round(msps / 40.0, 2), 'full': bool(args.full),
         'roofline': roofline,
         'kernels_ms': {k: round(v[1], 3) for k, v in sorted(stats.items(), key=lambda kv: -kv[1][1])},
         'cpu_baseline': cpu,
@@ -784,8 +910,6 @@ def main():
                          'exchange: the N = 1 rate of the per-rank work, so the N-rank value has a baseline on '
                          'its own workload (N x this = perfect scaling)' % world)}
     print(json.dumps(line), flush=True)
-    if dist is not None:
-        dist.destroy_process_group()
 
 
 if __name__ == '__main__':

@@ -10,6 +10,6 @@ mkdir -p gpurun_out
 bash tools/r06_t.sh ${TAG} 4
 bash tools/cli_e2e.sh ${TAG}
 timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-    --master-port 29517 bench.py --gpus 2 --steps 2 --warmup 1 --seconds 240 --no-cpu \
+    --master-port 29517 bench.py --full --gpus 2 --steps 2 --warmup 1 --seconds 240 --no-cpu \
     > gpurun_out/${TAG}_bench_sharded_240s_2rank_1gpu.json 2> gpurun_out/${TAG}_bench_sharded_2rank.err
 echo done

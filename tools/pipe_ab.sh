@@ -10,7 +10,7 @@ for i in $(seq 1 $REPS); do
   for cfg in "$@"; do
     envs=(); args=()
     for w in $cfg; do case $w in *=*) envs+=("$w");; *) args+=("$w");; esac; done
-    out=$(env "${envs[@]}" timeout -k 10 300 python bench.py --steps 6 --warmup 2 --no-cpu "${args[@]}" 2>/dev/null | tail -1)
+    out=$(env "${envs[@]}" timeout -k 10 300 python bench.py --full --steps 6 --warmup 2 --no-cpu "${args[@]}" 2>/dev/null | tail -1)
     echo "$cfg | $(echo "$out" | python3 -c 'import json,sys; d=json.load(sys.stdin); print(d["value"], d["ms_per_step"], d["roofline"]["avg_launch_ms"], d["checks"]["reads_decoded"])')"
   done
 done

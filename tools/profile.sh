@@ -13,11 +13,11 @@ mkdir -p $OUT
 if [ "$1" = notrace ]; then
   shift
 else
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python3 bench.py $ARGS > $OUT/trace.log 2>&1
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python3 bench.py --full $ARGS > $OUT/trace.log 2>&1
 fi
 i=0
 for grp in "$@"; do
   i=$((i+1))
-  timeout -s KILL 300 rocprofv3 --pmc $grp --output-format csv -d $OUT/pmc$i -o run -- python3 bench.py $ARGS > $OUT/pmc$i.log 2>&1
+  timeout -s KILL 300 rocprofv3 --pmc $grp --output-format csv -d $OUT/pmc$i -o run -- python3 bench.py --full $ARGS > $OUT/pmc$i.log 2>&1
 done
 echo done
