@@ -1082,6 +1082,10 @@ static void read_geometry(ReadDesc& r, int64_t start) {
   r.n_audio2 = r.n_audio / AUDIO_DIV2;
 }
 
+// ldg_k_probe_pick's half-window: it moves a probed read by at most this many samples
+// (0.3 lines; GPUDecoder.probe_win is the same figure)
+static int probe_halfwin(const SysConst& C) { return (int)(3 * (int64_t)C.linelen / 10); }
+
 int ldg_decode_reads_async2(ldg_ctx* ctx, int n, const int64_t* read_starts, const double* mtf,
                             const int32_t* slots, uint8_t* full) {
   if (!ctx || n <= 0 || n > ctx->max_reads || !read_starts || !mtf) return LDG_EINVAL;
@@ -1165,11 +1169,16 @@ int ldg_decode_reads_async2(ldg_ctx* ctx, int n, const int64_t* read_starts, con
   ctx->rf_cur = ctx->rf_tab[ci];
   if (ctx->cs && (ctx->stages & 1)) {
     // a streamed capture: the samples this call's blocks (and start probes) read are in
-    // the ring before its demod runs, and the kernels get the window they may read
+    // the ring before its demod runs, and the kernels get the window they may read.
+    // A read flagged LDG_READ_PROBE may be moved by ldg_k_probe_pick by up to the probe's
+    // half-window either way, and is flagged before it is known whether its probe runs:
+    // the window covers every flagged read's blocks at both ends of that range (a window
+    // cut at the predicted start's last block gave the moved read's last block FS_EOF)
     int64_t lo = INT64_MAX, hi = 0;
     for (int i = 0; i < n; i++) {
-      lo = std::min(lo, std::min(nr[i].s0, nr[i].readsample - PROBE_C - BLOCKCUT));
-      hi = std::max(hi, nr[i].s0 + (int64_t)(nr[i].n_blocks - 1) * BLOCKSTEP + BLOCKLEN);
+      const int64_t w = (full && (full[i] & LDG_READ_PROBE)) ? probe_halfwin(ctx->C) : 0;
+      lo = std::min(lo, std::min(nr[i].s0 - w, nr[i].readsample - PROBE_C - BLOCKCUT));
+      hi = std::max(hi, nr[i].s0 + (int64_t)(nr[i].n_blocks - 1) * BLOCKSTEP + BLOCKLEN + w);
     }
     if (int rc = stream_prepare(ctx, s, std::max<int64_t>(0, lo), hi)) return rc;
   }
@@ -1219,7 +1228,7 @@ int ldg_decode_reads_async2(ldg_ctx* ctx, int n, const int64_t* read_starts, con
                   ctx->d_status, ctx->d_ospill, ++ctx->park_epoch, ctx->d_stile, ctx->d_aslice, ctx->d_sst,
                   ctx->d_sbits, ctx->d_bst, nullptr);
     LDG_LAUNCH_ON(s, "probe_pick", ldg_k_probe_pick, np, 64, dps, ctx->d_preads, ctx->d_reads, ctx->d_status,
-                  ctx->d_sst, ctx->d_sbits, C, (int)(3 * (int64_t)C.linelen / 10));
+                  ctx->d_sst, ctx->d_sbits, C, probe_halfwin(C));
     if (int rc = check_launch(ctx, "ldg_k_probe_pick")) return rc;
     ctx->probes += np;
   }

@@ -31,8 +31,9 @@ from .rfparams import RFTables
 READLEN = 1000000
 BLOCKLEN, BLOCKCUT, BLOCKSTEP = 16384, 1024, 15328
 # a streamed capture keeps this many samples below the replay's position: a read's first
-# block (start - 1024) and its start probe's block (start - 7664 - 1024, moved by up to
-# 0.3 lines) begin there at most
+# block (start - 1024; a probed read may be moved down by the probe's half-window, 0.3
+# lines = 762 / 768 samples, first) and its start probe's block (start - 7664 - 1024, which
+# does not move) begin at most 8688 samples below a start the replay can still ask for
 STREAM_MARGIN = 32768
 
 
@@ -212,6 +213,12 @@ class GPUDecoder:
     frame, re-using every read already decoded.
     """
 
+    # the start probes' state before __init__ sets it: off, nothing planned or decoded
+    # (_stream_fit reads it, also on a decoder the tests build without a GPU)
+    probe, probe_win = False, 0
+    plan_guessed = full_keys = frozenset()
+    _hint_keys = ()
+
     def __init__(self, system='NTSC', device=0, batch=32, capacity=None, log=None):
         self.rf = RFTables(system)
         self.sysp = self.rf.system
@@ -346,11 +353,17 @@ class GPUDecoder:
 
     def _stream_fit(self, keys):
         """The leading keys a launch can decode from the stream's ring now: none below its
-        lowest readable sample, none ending past its reach.  With nothing in flight and no
+        lowest readable sample, none ending past its reach.  A read the launch will flag for
+        a start probe may be decoded up to the probe's half-window from its predicted start
+        (the library asks the ring for that much more, and the moved read's blocks must lie
+        inside it), so it needs that margin at both ends.  With nothing in flight and no
         key fitting, the stream restarts at the first key (a jump of the replay, a seek)."""
+        probing = self._will_probe()
+
         def span(k):
             s0, _, last = read_geometry(k[0])
-            return s0, min(last + BLOCKLEN, self.cap_nsamples)
+            w = self.probe_win if probing and self._probe_flag(k) else 0
+            return s0 - w, min(last + BLOCKLEN + w, self.cap_nsamples)
         for attempt in range(2):
             lo, reach, _, _ = self.ctx.stream_window()
             n = 0
@@ -593,6 +606,9 @@ class GPUDecoder:
         entries not in `protect` (the reads the replay is about to consume) as
         needed; _launch_wait() adds the records of the oldest launch to the cache.
         Slots of launches still in flight are never reused."""
+        if self.probe_mode == 'auto' and not self.probe:
+            j = self.stats.get('jitter_misses', 0)
+            self.probe = j > 3 and j > 0.01 * self.stats['reads_used']
         if self.stream:
             keys = self._stream_fit(keys)
             if not keys:
@@ -614,16 +630,11 @@ class GPUDecoder:
             raise RuntimeError('read cache full (capacity %d)' % self.capacity)
         slots = free[:len(keys)]
         t0 = time.perf_counter()
-        if self.probe_mode == 'auto' and not self.probe:
-            j = self.stats.get('jitter_misses', 0)
-            self.probe = j > 3 and j > 0.01 * self.stats['reads_used']
-        # (not the very first launch: its guesses at the nominal field spacing are not near
-        # field starts, they only locate the first fields)
-        probe = self.probe and bool(self.plan_guessed) and bool(self._hint_keys)
+        probe = self._will_probe()
         full = None
         if self.full_keys or probe:
             full = [(native.READ_FULL if k in self.full_keys else 0) |
-                    (native.READ_PROBE if probe and k in self.plan_guessed and k not in self.full_keys else 0)
+                    (native.READ_PROBE if probe and self._probe_flag(k) else 0)
                     for k in keys]
         back = self.ctx.decode_reads_async([k[0] for k in keys], [k[1] for k in keys], slots, full)
         if back is not None:
@@ -644,6 +655,16 @@ class GPUDecoder:
         self.pending.append((keys, slots))
         self.inflight.update(keys)
         return True
+
+    def _will_probe(self):
+        """The next launch probes its guessed reads' starts.  (Not the very first launch: its
+        guesses at the nominal field spacing are not near field starts, they only locate the
+        first fields.)"""
+        return self.probe and bool(self.plan_guessed) and bool(self._hint_keys)
+
+    def _probe_flag(self, k):
+        """A probing launch flags this read READ_PROBE: its start came from a prediction."""
+        return k in self.plan_guessed and k not in self.full_keys
 
     def _launch_wait(self):
         if not self.pending:

@@ -94,12 +94,16 @@ class SynthRF:
     """Chunked generator.  ``generate(n)`` returns float64 RF; ``encode`` quantises."""
 
     def __init__(self, system='NTSC', first_frame=1, clv=False, seed=20181015, noise=0.02,
-                 start_line=100, audio=True, bars=True, code_fields=(0, 1), frame_skip=None, dropouts=()):
+                 start_line=100, audio=True, bars=True, code_fields=(0, 1), frame_skip=None, dropouts=(),
+                 wow=()):
         self.p = NTSC if system == 'NTSC' else PAL
         p = self.p
         self.spl = FS * p['line_us'] / 1e6          # samples per line (2542.22 / 2560)
         self.codes = FrameCodes(first_frame, clv, 30 if system == 'NTSC' else 25, skip=frame_skip)
         self.dropouts = tuple(dropouts)              # (first sample, count): RF replaced by noise
+        # time-base error (wow and flutter): (amp, period in samples, phase) components of the
+        # disc's speed 1 + sum amp sin(2 pi n / period + phase) against the capture clock
+        self.wow = tuple((float(a), float(per), float(ph)) for a, per, ph in wow)
         self.seed, self.noise, self.audio = seed, noise, audio
         self.t0_lines = start_line                  # capture starts this many lines into frame 0
         self.bars = bars
@@ -118,8 +122,17 @@ class SynthRF:
         self.chunk_index = 0
 
     # -- baseband --------------------------------------------------------------
+    def disc_time(self, n):
+        """The disc's time, in nominal samples, at capture samples ``n``: the integral of
+        the speed from sample 0, in closed form (so a capture does not depend on its chunks)."""
+        tau = n.astype(np.float64)
+        for amp, per, ph in self.wow:
+            tau -= amp * per / (2 * np.pi) * (np.cos(2 * np.pi * n / per + ph) - np.cos(ph))
+        return tau
+
     def _ire(self, n):
-        """Hard-edged composite IRE at absolute sample indices ``n`` (int64)."""
+        """Hard-edged composite IRE at absolute sample indices ``n`` (int64, or the float
+        disc time of a capture with time-base error)."""
         p = self.p
         H = p['line_us']
         L = p['lines']
@@ -221,10 +234,25 @@ class SynthRF:
         return out
 
     # -- RF ----------------------------------------------------------------------
+    WOW_BLOCK = 1 << 16
+
     def generate(self, count):
+        """The next ``count`` samples.  A rigid capture's noise and FM phase carry depend on
+        the chunks it is generated in (the golden captures pin chunks of 2^22).  One with
+        time-base error does not: it is generated in steps that end at the multiples of
+        WOW_BLOCK, with the noise drawn per block and the phase reduced only there."""
+        if not self.wow:
+            return self._generate(count)
+        parts, end = [], self.pos + count
+        while self.pos < end:
+            parts.append(self._generate(min(end, (self.pos // self.WOW_BLOCK + 1) * self.WOW_BLOCK) - self.pos))
+        return np.concatenate(parts)
+
+    def _generate(self, count):
         p = self.p
         n = np.arange(self.pos, self.pos + count, dtype=np.int64)
-        ire = self._ire(n)
+        # the picture follows the disc; filters, FM phase, audio carriers and noise the capture clock
+        ire = self._ire(self.disc_time(n) if self.wow else n)
         hz = p['ire0'] + p['hz_ire'] * ire
         # band-limit (carrying FIR history) then pre-emphasis (carrying IIR state)
         ext = np.concatenate([self.fir_hist, hz])
@@ -232,15 +260,26 @@ class SynthRF:
         self.fir_hist = ext[-(len(self.fir) - 1):]
         emph, self.zi = sps.lfilter(self.b_emp, self.a_emp, bl, zi=self.zi)
         dph = (2 * np.pi / FS) * emph
-        ph = self.phase + np.cumsum(dph)
+        if self.wow:
+            # one running sum from the carried phase: the same additions however it is split
+            ph = np.cumsum(np.concatenate(([self.phase], dph)))[1:]
+            block_end = (self.pos + count) % self.WOW_BLOCK == 0
+            self.phase = float(np.mod(ph[-1], 2 * np.pi)) if block_end else float(ph[-1])
+        else:
+            ph = self.phase + np.cumsum(dph)
+            self.phase = float(np.mod(ph[-1], 2 * np.pi))
         rf = np.cos(ph)
-        self.phase = float(np.mod(ph[-1], 2 * np.pi))
         if self.audio:
             t = n / FS
             for fc, fm in ((p['audio_l'], 1000.0), (p['audio_r'], 400.0)):
                 frac = np.mod(n * (fc / FS), 1.0)
                 rf += 0.1 * np.cos(2 * np.pi * frac + (50000.0 / fm) * np.sin(2 * np.pi * fm * t))
-        if self.noise:
+        if self.noise and self.wow:
+            blk = self.pos // self.WOW_BLOCK             # (this step lies inside one block)
+            rng = np.random.default_rng([self.seed, 11, blk])
+            o = self.pos - blk * self.WOW_BLOCK
+            rf += rng.normal(0.0, self.noise, self.WOW_BLOCK)[o:o + count]
+        elif self.noise:
             rng = np.random.default_rng([self.seed, self.chunk_index])
             rf += rng.normal(0.0, self.noise, count)
         for d0, dn in self.dropouts:

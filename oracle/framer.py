@@ -196,10 +196,12 @@ def field_record(f):
     return rec
 
 
-def decode_capture(data, fmt, system='NTSC', start=0, length=None, seek=-1, log=None):
+def decode_capture(data, fmt, system='NTSC', start=0, length=None, seek=-1, log=None, on_field=None):
     """The lddecode.py:39-107 decode loop (no cut mode).
 
     Returns (tbc_frames list[np.uint16 array], pcm list[np.int16 array], meta list[dict]).
+    on_field(field) sees every Field the framer builds, in read order (tests that look at the
+    decode's own line locations).
     """
     log = log or (lambda *a, **k: None)
     rf = RFDemod(system=system)
@@ -228,6 +230,9 @@ def decode_capture(data, fmt, system='NTSC', start=0, length=None, seek=-1, log=
                                               for k, v in framer.vbi.items()},
                          'nextsample': int(nextsample),
                          'fields': [field_record(x) for x in framer.field_log[nlog:]]})
+            if on_field is not None:
+                for x in framer.field_log[nlog:]:
+                    on_field(x)
         else:
             break
     return frames, pcm, meta

@@ -19,7 +19,7 @@ sys.path.insert(0, os.path.join(ROOT, 'ld-decode_amd'))
 
 import numpy as np  # noqa: E402
 
-from ldgpu.synth import make_capture  # noqa: E402
+from ldgpu.synth import NTSC, PAL, make_capture  # noqa: E402
 from oracle.capture import FMT_BY_EXT, Capture  # noqa: E402
 from oracle.comb import Comb2D  # noqa: E402
 from oracle.demod import RFDemod  # noqa: E402
@@ -51,6 +51,44 @@ CASES = {
     'pal_clv_lds_0p15s': dict(seconds=0.15, fmt='lds', system='PAL', kw={'clv': True, 'first_frame': 3000, 'seed': 14}),
     'pal_cav_r30_0p15s': dict(seconds=0.15, fmt='r30', system='PAL', kw={'seed': 15}),
 }
+
+
+def wow(system, amp1, amp2, phase2=1.1):
+    """Two disc-speed components (SynthRF's ``wow``): a flutter of 37.3 lines' period and a
+    wow of 1.7 fields' period, so that no two lines or fields of a capture see the same error."""
+    spl = 40e6 * (NTSC if system == 'NTSC' else PAL)['line_us'] / 1e6
+    field_lines = 262.5 if system == 'NTSC' else 312.5
+    return ((amp1, 37.3 * spl, 0.4), (amp2, 1.7 * field_lines * spl, phase2))
+
+
+# captures with time-base error: every capture above comes from a rigid clock (line spans
+# 2542 +- 1 / 2560 +- 1 samples), which leaves the time-base corrector at its fixed point
+CASES.update({
+    # line spans ~ +-9 samples around nominal, nextfieldoffset hundreds of samples off the clean chain
+    'ntsc_cav_u8_wow_0p2s': dict(seconds=0.2, fmt='u8', system='NTSC',
+                                 kw={'seed': 31, 'wow': wow('NTSC', 0.0015, 0.002)}),
+    # line spans ~ +-25 samples: gaps outside linelen +- 0.2 us, so refine_linelocs_hsync's head /
+    # tail repair replaces them (lddecode_core.py:767-785); frames off nominal by more than the
+    # planner's probe half-window (762 samples; with the wow at the other cases' phase 1.1 the
+    # three frame lengths of 0.2 s stay within 728 of nominal, at 0.35 the first is ~790 short)
+    'ntsc_cav_u8_wowbig_0p2s': dict(seconds=0.2, fmt='u8', system='NTSC',
+                                    kw={'seed': 31, 'wow': wow('NTSC', 0.006, 0.004, phase2=0.35)}),
+    'pal_clv_u8_wow_0p25s': dict(seconds=0.25, fmt='u8', system='PAL',
+                                 kw={'clv': True, 'first_frame': 3000, 'seed': 31,
+                                     'wow': wow('PAL', 0.0015, 0.002)}),
+    'pal_cav_u8_wowbig_0p25s': dict(seconds=0.25, fmt='u8', system='PAL',
+                                    kw={'seed': 31, 'wow': wow('PAL', 0.006, 0.004)}),
+    # frame lengths a few to tens of samples off nominal: inside the probe window, outside the
+    # planner's exact prediction
+    'ntsc_cav_u8_jit_0p3s': dict(seconds=0.3, fmt='u8', system='NTSC',
+                                 kw={'seed': 31, 'wow': wow('NTSC', 0.00002, 0.0001)}),
+    'pal_clv_u8_jit_0p3s': dict(seconds=0.3, fmt='u8', system='PAL',
+                                kw={'clv': True, 'first_frame': 3000, 'seed': 31,
+                                    'wow': wow('PAL', 0.00002, 0.0001)}),
+    # the same timing behind the 10-bit .lds packing groups
+    'ntsc_cav_lds_wow_0p15s': dict(seconds=0.15, fmt='lds', system='NTSC',
+                                   kw={'seed': 31, 'wow': wow('NTSC', 0.0015, 0.002)}),
+})
 
 
 def sha(b):

@@ -40,13 +40,23 @@ class _FakeStreamCtx:
         self.win = [s - s % 12, s - s % 12 + (self.win[1] - self.win[0])]
 
 
-def _fit(lo, reach, keys, pending=()):
+PROBE_WIN = 762          # GPUDecoder.probe_win on NTSC: int(0.3 * rf.linelen)
+
+
+def _fit(lo, reach, keys, pending=(), probing=False, guessed=None):
+    """_stream_fit on a decoder without a GPU.  probing: the decoder's probes are on and a
+    decoded read is known (the launch will probe); guessed: the keys whose start the plan
+    predicted (default: all of them), which are the ones that launch flags READ_PROBE."""
     from ldgpu.decoder import GPUDecoder
     d = GPUDecoder.__new__(GPUDecoder)
     d.ctx = _FakeStreamCtx(lo, reach)
     d.pending = list(pending)
     d.cap_nsamples = 10 ** 9
     d.stats = {}
+    if probing:          # (otherwise the class's own defaults: probes off, nothing planned)
+        d.probe, d.probe_win = True, PROBE_WIN
+        d.plan_guessed = set(keys if guessed is None else guessed)
+        d._hint_keys = [keys[0][0] - 667000]
     return d, d._stream_fit(keys)
 
 
@@ -72,6 +82,36 @@ def test_stream_fit_restarts_the_stream_at_a_jump():
     assert fit == [] and not d.ctx.seeks
 
 
+def test_stream_fit_leaves_room_for_a_moved_probe():
+    """A read flagged READ_PROBE is decoded up to the probe's half-window from its predicted
+    start (ldg_k_probe_pick), and the library asks the ring for that much more: such a key is
+    launched only with the half-window free past its last block and below its first one.
+    Unflagged keys of the same launch, and every key with the probes off, fit exactly."""
+    from ldgpu.decoder import BLOCKLEN, read_geometry
+    keys = [(1000000 + 667000 * i, 1.0) for i in range(10)]
+    first = lambda k: read_geometry(k[0])[0]                        # noqa: E731
+    last_end = lambda k: read_geometry(k[0])[2] + BLOCKLEN          # noqa: E731
+    reach = last_end(keys[4])
+    assert _fit(0, reach, keys)[1] == keys[:5]                       # probes off: as before
+    d, fit = _fit(0, reach, keys, probing=True)
+    assert fit == keys[:4] and not d.ctx.seeks                       # ends exactly at reach: not launched
+    assert _fit(0, reach + PROBE_WIN - 1, keys, probing=True)[1] == keys[:4]
+    assert _fit(0, reach + PROBE_WIN, keys, probing=True)[1] == keys[:5]
+    # the same at the low end: the moved read's first block may begin that much lower
+    lo = first(keys[0])
+    assert _fit(lo, reach, keys, pending=[1])[1] == keys[:5]
+    assert _fit(lo, reach + PROBE_WIN, keys, pending=[1], probing=True)[1] == []
+    assert _fit(lo - PROBE_WIN + 1, reach + PROBE_WIN, keys, pending=[1], probing=True)[1] == []
+    assert _fit(lo - PROBE_WIN, reach + PROBE_WIN, keys, pending=[1], probing=True)[1] == keys[:5]
+    # only the reads the launch flags (the plan's guesses) need the margin
+    assert _fit(lo, reach, keys, pending=[1], probing=True, guessed=keys[5:])[1] == keys[:5]
+    assert _fit(lo, reach, keys, pending=[1], probing=True, guessed=keys[4:])[1] == keys[:4]
+    # a launch never asks the ring for more than its reach (LDG_ESTATE 'a read ends past the ring')
+    for extra in (0, 1, PROBE_WIN - 1, PROBE_WIN, 5000):
+        _, fit = _fit(0, reach + extra, keys, probing=True)
+        assert all(last_end(k) + PROBE_WIN <= reach + extra for k in fit)
+
+
 def test_stream_abi_declared():
     src = open(os.path.join(ROOT, 'include', 'ldgpu.h')).read()
     for f in ('ldg_stream_open', 'ldg_stream_release', 'ldg_stream_seek', 'ldg_stream_window',
@@ -86,7 +126,12 @@ def test_stream_abi_declared():
                                           ('ntsc_cav_s16_0p15s', 6),
                                           ('ntsc_cav_r30_0p15s', 2), ('ntsc_cav_lds_0p15s', 2),
                                           ('pal_clv_u8_0p2s', 2), ('ntsc_cav_u8_mtf_0p3s', 4),
-                                          ('ntsc_cav_u8_mid_0p2s', 2)])
+                                          ('ntsc_cav_u8_mid_0p2s', 2),
+                                          # time-base error: frames tens of samples off nominal
+                                          # (probed reads move) and hundreds (past the probe window)
+                                          ('ntsc_cav_u8_jit_0p3s', 2), ('pal_clv_u8_jit_0p3s', 2),
+                                          ('ntsc_cav_u8_wowbig_0p2s', 2), ('pal_cav_u8_wowbig_0p25s', 2),
+                                          ('ntsc_cav_lds_wow_0p15s', 2)])
 def test_stream_decode_equals_resident(case, ring_mb, tmp_path):
     """Every golden case through a ring of a few MiB (the capture slides through it many
     times over; u8 2 MiB = 3 fields) gives exactly the resident decode, which the golden
@@ -117,6 +162,41 @@ def test_stream_decode_equals_resident(case, ring_mb, tmp_path):
     assert st['bytes_read'] >= len(data) * 0.9 and st['ring_bytes'] <= ring_mb << 20
     print('%s: ring %d MiB, %d chunks, %d launch waits, %d seeks' % (case, ring_mb, st['chunks'],
                                                                      st['launch_waits'], st['seeks']))
+    dec.ctx.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('case', ['ntsc_cav_u8_jit_0p3s', 'ntsc_cav_u8_wowbig_0p2s'])
+def test_stream_decode_with_moved_probes(case, tmp_path, monkeypatch):
+    """NTSC with the start probes forced on (LDG_PROBE=1; its default turns them on only
+    after jitter misses) on captures whose field starts are off the planner's grid: probes
+    move reads, also the highest read of a launch, whose last block then lies past the
+    window of the predicted starts.  The streamed decode through a 2 MiB ring is the
+    resident one, which the golden fixture pins."""
+    sys.path.insert(0, os.path.join(HERE, 'golden'))
+    import make_golden
+    from ldgpu.decoder import GPUDecoder
+    monkeypatch.setenv('LDG_PROBE', '1')
+    with open(os.path.join(HERE, 'golden', case + '.json')) as fh:
+        gold = json.load(fh)
+    data = make_golden.build_capture(case)
+    path = tmp_path / 'cap.u8'
+    path.write_bytes(bytes(data))
+    dec = GPUDecoder(system='NTSC', batch=16)
+    dec.set_capture(data, 0)
+    want = _decode(dec)
+    moved_resident = dec.stats.get('probe_moved', 0)
+    dec.open_stream(str(path), 0, 2 << 20)
+    got = _decode(dec)
+    moved = dec.stats.get('probe_moved', 0) - moved_resident
+    print('%s LDG_PROBE=1: probes %d, moved %d resident + %d streamed, reads %d, used %d' % (
+        case, dec.stats.get('probes', 0), moved_resident, moved, dec.stats['reads'], dec.stats['reads_used']))
+    assert moved_resident > 0 and moved > 0
+    assert len(got) == len(want) == len(gold['frames'])
+    for (f1, a1, m1), (f2, a2, m2), g in zip(got, want, gold['frames']):
+        assert m1 == m2 == g['meta']
+        assert np.array_equal(f1, f2)
+        assert np.array_equal(a1, a2)
     dec.ctx.close()
 
 
