@@ -973,7 +973,7 @@ int ldg_set_capture(ldg_ctx* ctx, const void* data, int64_t nsamples, int fmt, i
   return LDG_OK;
 }
 
-static int stream_prepare(ldg_ctx* ctx, hipStream_t s, int64_t lo, int64_t hi);   // stream.inc
+static int stream_prepare(ldg_ctx* ctx, hipStream_t s, int64_t hi);   // stream.inc
 
 // Profiling: the next demod launch's execution-span slot ({max ~start, max end}
 // on the device's constant-rate clock, zero-initialised), or null when not
@@ -1172,15 +1172,16 @@ int ldg_decode_reads_async2(ldg_ctx* ctx, int n, const int64_t* read_starts, con
     // the ring before its demod runs, and the kernels get the window they may read.
     // A read flagged LDG_READ_PROBE may be moved by ldg_k_probe_pick by up to the probe's
     // half-window either way, and is flagged before it is known whether its probe runs:
-    // the window covers every flagged read's blocks at both ends of that range (a window
-    // cut at the predicted start's last block gave the moved read's last block FS_EOF)
-    int64_t lo = INT64_MAX, hi = 0;
+    // the window's high end covers every flagged read's last block at the far end of that
+    // range (a window cut at the predicted start's last block gave the moved read's last
+    // block FS_EOF).  Its low end is the released point, which the host keeps STREAM_MARGIN
+    // below the replay (ldgpu/decoder.py): that covers a read moved back and its probe.
+    int64_t hi = 0;
     for (int i = 0; i < n; i++) {
       const int64_t w = (full && (full[i] & LDG_READ_PROBE)) ? probe_halfwin(ctx->C) : 0;
-      lo = std::min(lo, std::min(nr[i].s0 - w, nr[i].readsample - PROBE_C - BLOCKCUT));
       hi = std::max(hi, nr[i].s0 + (int64_t)(nr[i].n_blocks - 1) * BLOCKSTEP + BLOCKLEN + w);
     }
-    if (int rc = stream_prepare(ctx, s, std::max<int64_t>(0, lo), hi)) return rc;
+    if (int rc = stream_prepare(ctx, s, hi)) return rc;
   }
   // start probes: the one block centred on each flagged read's (predicted) start,
   // where it lies inside the capture

@@ -2,11 +2,10 @@
 // 16,384-sample block from the file when the demod needs it (lddutils.py:131-229, called
 // per block from RFDecode.demod, lddecode_core.py:373-392), so a capture of any length
 // decodes in O(1) memory.  Here a reader thread streams the file, chunk by chunk, through
-// pinned staging into a ring in HBM on its own copy stream, ahead of the decode:
-//
-//   file bytes [base_b, fed_b) have been queued into the ring (byte b at b mod R, the ring's
-//   first TAIL bytes mirrored after it so a block never wraps); the host promises, through
-//   ldg_stream_release, that no launch after the call reads bytes below release_b.
+// pinned staging into a ring in HBM on its own copy stream, ahead of the decode.  What is
+// queued, released and waited on is decided by stream_core.hpp (no device call there, so a
+// CPU driver tests it); this file holds the device and OS resources and does what the core
+// returns.
 //
 // A chunk may overwrite ring space only once it is released AND the launches that could
 // still read it have finished: each release records events on both demod streams, and the
@@ -15,216 +14,87 @@
 // of the last of them, and runs with the window [release, its highest block end): reads
 // outside it come back FS_EOF.  No cycle: a launch is issued only after its chunks were
 // queued, and every later chunk waits only on launches issued before its release.
-#include <condition_variable>
-#include <deque>
 #include <fcntl.h>
-#include <mutex>
 #include <sys/stat.h>
-#include <unistd.h>
 
-// A chunk's read(2) split over helper threads: the reader's loop is serial (read a chunk,
-// queue its copy), and a 60 s u8 step reads 2.4 GB in the ~85 ms the decode takes; with
-// four helpers the reads take ~45 ms of it (ldg_stream_stats read_s, profiles/r06_t_*).
-struct ReadPool {
-  static constexpr int64_t ALIGN = 1 << 16;
-  std::mutex m;
-  std::condition_variable cv, done_cv;
-  std::vector<std::thread> th;
-  uint64_t gen = 0;
-  int fd = -1, pending = 0;
-  uint8_t* dst = nullptr;
-  int64_t len = 0, off = 0;
-  bool quit = false, err = false;
-
-  void start(int n) {
-    for (int i = 0; i < n; i++) th.emplace_back([this, i, n] { run(i, n); });
-  }
-  void run(int i, int n) {
-    uint64_t seen = 0;
-    std::unique_lock<std::mutex> lk(m);
-    for (;;) {
-      cv.wait(lk, [&] { return quit || gen != seen; });
-      if (quit) return;
-      seen = gen;
-      const int64_t part = ((len + n - 1) / n + ALIGN - 1) / ALIGN * ALIGN;
-      const int64_t a = std::min(len, i * part), b = std::min(len, a + part);
-      const int f = fd;
-      uint8_t* d = dst;
-      const int64_t o = off;
-      lk.unlock();
-      bool ok = true;
-      for (int64_t got = a; got < b;) {
-        const ssize_t r = pread(f, d + got, (size_t)(b - got), (off_t)(o + got));
-        if (r <= 0) { ok = false; break; }
-        got += r;
-      }
-      lk.lock();
-      if (!ok) err = true;
-      if (--pending == 0) done_cv.notify_all();
-    }
-  }
-  // bytes [o, o + l) of f into d, on every helper; false on a short read or an error
-  bool read(int f, uint8_t* d, int64_t l, int64_t o) {
-    std::unique_lock<std::mutex> lk(m);
-    fd = f; dst = d; len = l; off = o;
-    pending = (int)th.size();
-    err = false;
-    gen++;
-    cv.notify_all();
-    done_cv.wait(lk, [&] { return pending == 0; });
-    return !err;
-  }
-  void stop() {
-    {
-      std::lock_guard<std::mutex> lk(m);
-      quit = true;
-      cv.notify_all();
-    }
-    for (auto& t : th)
-      if (t.joinable()) t.join();
-    th.clear();
-  }
-};
+#include "stream_core.hpp"
 
 struct CapStream {
   int fd = -1;
-  int fmt = 0;
-  int spg = 1, bpg = 1;                  // samples / bytes per packing group
-  int64_t file_bytes = 0, total_nsamp = 0;
-  int64_t chunk = 0;                     // reader step (bytes; a multiple of 20: every format's group)
-  int64_t R = 0;                         // ring bytes (a multiple of chunk)
-  static constexpr int64_t TAIL = 65536; // mirrored head: > one s16 block + a group + 16-B load slack
   uint8_t* ring = nullptr;               // device, R + TAIL bytes
   // Copy streams, chunk c on copy[c % ncopy]: one stream is one DMA engine, and one
   // engine's host-to-device rate is below what the decode consumes (a 60 s u8 step:
   // 1 stream 108 ms, 2 91 ms, 4 86.6 ms against 83 ms resident; profiles/r06_t_*).
-  static constexpr int NCOPY_MAX = 4;
-  hipStream_t copy[NCOPY_MAX] = {};
-  int ncopy = NCOPY_MAX;
+  hipStream_t copy[StreamCore::NCOPY_MAX] = {};
   static constexpr int NSTG = 8;
   uint8_t* stg[NSTG] = {};               // pinned staging, chunk bytes each
   hipEvent_t ev_stg[NSTG] = {};
   bool stg_used[NSTG] = {};
   int stg_next = 0;
   std::vector<hipEvent_t> ev_chunk;      // per ring chunk: the copy of its last fill
-  static constexpr int NREL = 256;
-  hipEvent_t ev_rel[NREL][2] = {};       // release records: events on the two demod streams
-  std::deque<std::pair<int64_t, int>> rel;   // (release byte, record), oldest first
-  std::vector<int> rel_free;
-  std::mutex mu;
-  std::condition_variable cv;
-  int64_t base_b = 0, fed_b = 0, release_b = 0;
-  bool stop = false, failed = false, started = false;
-  std::string err;
+  hipEvent_t ev_rel[StreamCore::NREL][2] = {};   // release records: events on the two demod streams
   std::thread th;
   static constexpr int NREADERS = 4;     // ReadPool helpers (the box gives a GPU 16 CPUs)
   ReadPool pool;
-  // statistics (ldg_stream_stats)
-  int64_t bytes_read = 0, chunks = 0, launch_waits = 0, seeks = 0;
-  double read_s = 0, space_wait_s = 0, launch_wait_s = 0, stage_wait_s = 0;
-
-  int64_t byte_of(int64_t s) const { return s / spg * bpg; }                    // group start
-  // the furthest the reader can fill before the next release: whole chunks (file-aligned)
-  // whose space lies above the released point
-  int64_t reach_b() const { return std::min(file_bytes, (release_b + R) / chunk * chunk); }
-  int64_t byte_end(int64_t e) const { return (e + spg - 1) / spg * bpg; }        // through sample e - 1
-  int64_t sample_ceil(int64_t b) const { return (b + bpg - 1) / bpg * spg; }     // first whole group at or after b
+  StreamCore core;
 };
-
-static double since(std::chrono::steady_clock::time_point t) {
-  return std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count();
-}
 
 static void stream_reader(ldg_ctx* ctx, CapStream* cs) {
   (void)hipSetDevice(ctx->device);
-  auto fail = [&](const std::string& m) {
-    std::lock_guard<std::mutex> lk(cs->mu);
-    cs->failed = true;
-    cs->err = m;
-    cs->cv.notify_all();
-  };
-  int64_t fb;
-  {
-    std::lock_guard<std::mutex> lk(cs->mu);
-    fb = cs->fed_b;
-  }
-  while (true) {
-    int64_t len;
-    int rec = -1;
-    {
-      std::unique_lock<std::mutex> lk(cs->mu);
-      if (cs->stop || fb >= cs->file_bytes) return;
-      len = std::min(cs->chunk - fb % cs->chunk, cs->file_bytes - fb);
-      const int64_t over = fb + len - cs->R;       // this chunk overwrites bytes below `over`
-      if (over > cs->base_b) {
-        const auto t0 = std::chrono::steady_clock::now();
-        cs->cv.wait(lk, [&] { return cs->stop || cs->release_b >= over; });
-        cs->space_wait_s += since(t0);
-        if (cs->stop) return;
-        // the first release record covering the space; older ones are implied by it
-        while (!cs->rel.empty() && cs->rel.front().first < over) {
-          cs->rel_free.push_back(cs->rel.front().second);
-          cs->rel.pop_front();
-        }
-        rec = cs->rel.front().second;              // exists: release_b >= over was recorded
-      }
-    }
+  StreamCore& core = cs->core;
+  StreamCore::Fill f;
+  while (core.next_fill(f)) {
     const int k = cs->stg_next;
     cs->stg_next = (k + 1) % CapStream::NSTG;
     const auto ts = std::chrono::steady_clock::now();
-    if (cs->stg_used[k] && hipEventSynchronize(cs->ev_stg[k]) != hipSuccess) return fail("stream: staging sync");
-    const double stage_wait = since(ts);
+    if (cs->stg_used[k] && hipEventSynchronize(cs->ev_stg[k]) != hipSuccess) return core.fail("stream: staging sync");
+    const double stage_wait = StreamCore::since(ts);
     const auto t0 = std::chrono::steady_clock::now();
-    if (!cs->pool.read(cs->fd, cs->stg[k], len, fb))
-      return fail(std::string("stream: read failed in bytes [") + std::to_string(fb) + ", " +
-                  std::to_string(fb + len) + ")");
-    {
-      std::lock_guard<std::mutex> lk(cs->mu);
-      cs->read_s += since(t0);
-      cs->stage_wait_s += stage_wait;
-      cs->bytes_read += len;
-      if (cs->stop) return;
-      hipError_t e = hipSuccess;
-      hipStream_t cp = cs->copy[(fb / cs->chunk) % cs->ncopy];
-      if (rec >= 0) {
-        if (e == hipSuccess) e = hipStreamWaitEvent(cp, cs->ev_rel[rec][0], 0);
-        if (e == hipSuccess) e = hipStreamWaitEvent(cp, cs->ev_rel[rec][1], 0);
-      }
-      const int64_t ro = fb % cs->R;
-      if (e == hipSuccess) e = hipMemcpyAsync(cs->ring + ro, cs->stg[k], len, hipMemcpyHostToDevice, cp);
-      if (e == hipSuccess && ro < CapStream::TAIL)
-        e = hipMemcpyAsync(cs->ring + cs->R + ro, cs->stg[k], std::min(len, CapStream::TAIL - ro),
-                           hipMemcpyHostToDevice, cp);
-      if (e == hipSuccess) e = hipEventRecord(cs->ev_stg[k], cp);
-      if (e == hipSuccess) e = hipEventRecord(cs->ev_chunk[ro / cs->chunk], cp);
-      if (e != hipSuccess) {
-        cs->failed = true;
-        cs->err = std::string("stream: ") + hipGetErrorString(e);
-        cs->cv.notify_all();
-        return;
-      }
-      cs->stg_used[k] = true;
-      cs->chunks++;
-      fb += len;
-      cs->fed_b = fb;
-      cs->cv.notify_all();
+    if (!cs->pool.read(cs->fd, cs->stg[k], f.len, f.fb))
+      return core.fail(std::string("stream: read failed in bytes [") + std::to_string(f.fb) + ", " +
+                       std::to_string(f.fb + f.len) + ")");
+    std::lock_guard<std::mutex> lk(core.mu);
+    if (!core.fill_read_locked(f, StreamCore::since(t0), stage_wait)) return;
+    hipError_t e = hipSuccess;
+    hipStream_t cp = cs->copy[f.copy];
+    if (f.rec >= 0) {
+      if (e == hipSuccess) e = hipStreamWaitEvent(cp, cs->ev_rel[f.rec][0], 0);
+      if (e == hipSuccess) e = hipStreamWaitEvent(cp, cs->ev_rel[f.rec][1], 0);
     }
+    if (e == hipSuccess) e = hipMemcpyAsync(cs->ring + f.ro, cs->stg[k], f.len, hipMemcpyHostToDevice, cp);
+    if (e == hipSuccess && f.mirror)
+      e = hipMemcpyAsync(cs->ring + core.R + f.ro, cs->stg[k], f.mirror, hipMemcpyHostToDevice, cp);
+    if (e == hipSuccess) e = hipEventRecord(cs->ev_stg[k], cp);
+    if (e == hipSuccess) e = hipEventRecord(cs->ev_chunk[f.slot], cp);
+    if (e != hipSuccess) return core.fail_locked(std::string("stream: ") + hipGetErrorString(e));
+    cs->stg_used[k] = true;
+    core.fill_queued_locked(f);
   }
 }
 
-static void stream_stop(ldg_ctx* ctx, CapStream* cs) {
-  {
-    std::lock_guard<std::mutex> lk(cs->mu);
-    cs->stop = true;
-    cs->cv.notify_all();
-  }
+static void stream_stop(CapStream* cs) {
+  cs->core.request_stop();
   if (cs->th.joinable()) cs->th.join();
-  (void)ctx;
+}
+
+// The one place that points the context's capture at the ring (window [first, first + nsamp))
+static void stream_attach(ldg_ctx* ctx, const CapStream* cs, int64_t first, int64_t nsamp) {
+  ctx->cap = cs->ring;
+  ctx->cap_ring = cs->core.R;
+  ctx->cap_first = first;
+  ctx->cap_nsamp = nsamp;
+}
+
+// ... and away from it
+static void stream_detach(ldg_ctx* ctx, const CapStream* cs) {
+  if (ctx->cap != cs->ring) return;
+  ctx->cap = nullptr;
+  ctx->cap_ring = 0;
 }
 
 static void stream_free(ldg_ctx* ctx, CapStream* cs) {
   if (!cs) return;
-  stream_stop(ctx, cs);
+  stream_stop(cs);
   cs->pool.stop();
   (void)hipSetDevice(ctx->device);
   for (hipStream_t c : cs->copy)
@@ -244,91 +114,42 @@ static void stream_free(ldg_ctx* ctx, CapStream* cs) {
     if (c) (void)hipStreamDestroy(c);
   if (cs->ring) (void)hipFree(cs->ring);
   if (cs->fd >= 0) close(cs->fd);
-  if (ctx->cap == cs->ring) {
-    ctx->cap = nullptr;
-    ctx->cap_ring = 0;
-  }
+  stream_detach(ctx, cs);
   delete cs;
 }
 
 // (Re)start the reader at the packing group holding `sample`: nothing of the old window
 // is kept.  The caller has no decode outstanding that reads the ring.
 static int stream_restart(ldg_ctx* ctx, CapStream* cs, int64_t sample) {
-  stream_stop(ctx, cs);
-  for (int j = 0; j < cs->ncopy; j++) LDG_TRY(hipStreamSynchronize(cs->copy[j]));
+  stream_stop(cs);
+  for (int j = 0; j < cs->core.ncopy; j++) LDG_TRY(hipStreamSynchronize(cs->copy[j]));
   LDG_TRY(hipStreamSynchronize(ctx->stream));
   LDG_TRY(hipStreamSynchronize(ctx->stream_b));
-  sample = std::max<int64_t>(0, std::min(sample, cs->total_nsamp));
-  cs->base_b = cs->fed_b = cs->release_b = cs->byte_of(sample);
-  for (auto& r : cs->rel) cs->rel_free.push_back(r.second);
-  cs->rel.clear();
-  cs->stop = cs->failed = false;
-  cs->err.clear();
+  cs->core.restart(sample);
   cs->th = std::thread(stream_reader, ctx, cs);
   return LDG_OK;
 }
 
-// Before a launch on stream s whose blocks read samples [lo, hi): wait until the reader has
-// queued them, make s wait for their copy, and set the kernels' capture window.
-static int stream_prepare(ldg_ctx* ctx, hipStream_t s, int64_t lo, int64_t hi) {
+// Before a launch on stream s whose blocks read samples up to hi: wait until the reader has
+// queued them, make s wait for their copy, and set the kernels' capture window (its low end
+// is the released point).
+static int stream_prepare(ldg_ctx* ctx, hipStream_t s, int64_t hi) {
   CapStream* cs = ctx->cs;
-  hi = std::min(hi, cs->total_nsamp);
-  int64_t need = cs->byte_end(hi);
-  int64_t win_lo;
+  StreamCore::Launch l;
   {
-    std::unique_lock<std::mutex> lk(cs->mu);
-    if (need > cs->reach_b()) {
-      ctx->err = "stream: a read ends past the ring (release older samples first: ldg_stream_release)";
-      return LDG_ESTATE;
+    std::unique_lock<std::mutex> lk(cs->core.mu);
+    l = cs->core.prepare_locked(lk, hi, std::chrono::seconds(60));
+    if (l.st != StreamCore::OK) {
+      ctx->err = l.err;
+      return l.st == StreamCore::PAST_RING ? LDG_ESTATE : LDG_EDEVICE;
     }
-    if (cs->fed_b < need && !cs->failed) {
-      const auto t0 = std::chrono::steady_clock::now();
-      cs->launch_waits++;
-      // (bounded: the reader reaches `need` unless it failed; a stall is reported, not waited out)
-      const bool ok = cs->cv.wait_for(lk, std::chrono::seconds(60), [&] {
-        return cs->failed || cs->fed_b >= need || cs->fed_b >= cs->file_bytes;
-      });
-      cs->launch_wait_s += since(t0);
-      if (!ok) {
-        ctx->err = "stream: the reader did not reach byte " + std::to_string(need) + " within 60 s";
-        return LDG_EDEVICE;
-      }
-    }
-    if (cs->failed) {
-      ctx->err = cs->err;
-      return LDG_EDEVICE;
-    }
-    need = std::min(need, cs->fed_b);
-    win_lo = cs->sample_ceil(cs->release_b);
-    // the copy of the last chunk the launch reads, on each copy stream (in-order streams:
-    // the earlier chunks on it are done with it); chunks wholly released are not read
-    const int64_t last = (need - 1) / cs->chunk;
-    for (int64_t c = last; c > last - cs->ncopy && c >= 0; c--) {
-      if ((c + 1) * cs->chunk <= std::max(cs->base_b, cs->release_b) || c * cs->chunk >= need) continue;
-      LDG_TRY(hipStreamWaitEvent(s, cs->ev_chunk[(c * cs->chunk % cs->R) / cs->chunk], 0));
-    }
+    for (int i = 0; i < l.nslot; i++) LDG_TRY(hipStreamWaitEvent(s, cs->ev_chunk[l.slot[i]], 0));
   }
-  const int64_t win_hi = std::max(win_lo, std::min(hi, need / cs->bpg * cs->spg));
-  ctx->cap = cs->ring;
-  ctx->cap_ring = cs->R;
-  ctx->cap_first = win_lo;
-  ctx->cap_nsamp = win_hi - win_lo;
-  (void)lo;
+  stream_attach(ctx, cs, l.win_lo, l.win_hi - l.win_lo);
   return LDG_OK;
 }
 
 extern "C" {
-
-static void stream_set_file(CapStream* cs, int fd, int64_t bytes, int fmt) {
-  cs->fd = fd;
-  cs->fmt = fmt;
-  cs->spg = fmt == 2 ? 3 : fmt == 3 ? 4 : 1;
-  cs->bpg = fmt == 1 ? 2 : fmt == 2 ? 4 : fmt == 3 ? 5 : 1;
-  cs->file_bytes = bytes;
-  cs->total_nsamp = cs->file_bytes / cs->bpg * cs->spg;
-  cs->bytes_read = cs->chunks = cs->launch_waits = cs->seeks = 0;
-  cs->read_s = cs->space_wait_s = cs->launch_wait_s = cs->stage_wait_s = 0;
-}
 
 int ldg_stream_open(ldg_ctx* ctx, const char* path, int fmt, int64_t ring_bytes, int64_t first_sample) {
   if (!ctx || !path || fmt < 0 || fmt > 3 || ring_bytes <= 0 || first_sample < 0) return LDG_EINVAL;
@@ -344,95 +165,75 @@ int ldg_stream_open(ldg_ctx* ctx, const char* path, int fmt, int64_t ring_bytes,
     ctx->err = std::string("stream: cannot open ") + path;
     return LDG_EINVAL;
   }
-  int ncopy = CapStream::NCOPY_MAX;
+  int ncopy = StreamCore::NCOPY_MAX;
   if (const char* nc = getenv("LDG_STREAM_COPIES"))   // tuning: copy streams (1 - 4)
-    ncopy = std::max(1, std::min(CapStream::NCOPY_MAX, atoi(nc)));
-  const int64_t chunk = std::min<int64_t>(8388600, ring_bytes / 4) / 20 * 20;
-  if (CapStream* old = ctx->cs) {
-    if (chunk == old->chunk && ring_bytes / chunk * chunk == old->R && ncopy == old->ncopy) {
-      // the same ring again (the next file of a job): keep its memory, streams and events
-      stream_stop(ctx, old);
-      close(old->fd);
-      stream_set_file(old, fd, st.st_size, fmt);
-      ctx->fmt = fmt;
-      if (const int rc = stream_restart(ctx, old, first_sample)) return rc;
-      ctx->cap = old->ring;
-      ctx->cap_ring = old->R;
-      ctx->cap_first = old->sample_ceil(old->base_b);
-      ctx->cap_nsamp = 0;
-      return LDG_OK;
-    }
-    stream_free(ctx, old);
-    ctx->cs = nullptr;
-  }
-  auto* cs = new CapStream();
-  cs->ncopy = ncopy;
-  stream_set_file(cs, fd, st.st_size, fmt);
-  cs->pool.start(CapStream::NREADERS);
-  cs->chunk = chunk;
-  if (cs->chunk < CapStream::TAIL) {
-    ctx->err = "stream: ring too small (at least 4 x 64 KiB)";
-    stream_free(ctx, cs);
-    return LDG_EINVAL;
-  }
-  cs->R = ring_bytes / cs->chunk * cs->chunk;
+    ncopy = std::max(1, std::min(StreamCore::NCOPY_MAX, atoi(nc)));
+  CapStream* cs = ctx->cs;
   int rc = LDG_OK;
-  if (hipMalloc(&cs->ring, (size_t)(cs->R + CapStream::TAIL)) != hipSuccess) rc = LDG_ENOMEM;
-  for (int j = 0; j < cs->ncopy && !rc; j++)
-    if (hipStreamCreateWithFlags(&cs->copy[j], hipStreamNonBlocking) != hipSuccess) rc = LDG_EDEVICE;
-  for (int k = 0; k < CapStream::NSTG && !rc; k++)
-    if (hipHostMalloc((void**)&cs->stg[k], (size_t)cs->chunk, hipHostMallocDefault) != hipSuccess ||
-        hipEventCreateWithFlags(&cs->ev_stg[k], hipEventDisableTiming) != hipSuccess)
-      rc = LDG_ENOMEM;
-  cs->ev_chunk.assign((size_t)(cs->R / cs->chunk), nullptr);
-  for (auto& e : cs->ev_chunk)
-    if (!rc && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) rc = LDG_EDEVICE;
-  for (int i = 0; i < CapStream::NREL && !rc; i++) {
-    for (auto& e : cs->ev_rel[i])
-      if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) rc = LDG_EDEVICE;
-    cs->rel_free.push_back(i);
+  if (cs && cs->core.same_ring(ring_bytes, ncopy)) {
+    // the same ring again (the next file of a job): keep its memory, streams and events
+    stream_stop(cs);
+    close(cs->fd);
+  } else {
+    stream_free(ctx, cs);
+    ctx->cs = nullptr;
+    cs = new CapStream();
+    cs->pool.start(CapStream::NREADERS);
+    if (!cs->core.configure(ring_bytes, ncopy)) {
+      close(fd);
+      ctx->err = "stream: ring too small (at least 4 x 64 KiB)";
+      stream_free(ctx, cs);
+      return LDG_EINVAL;
+    }
+    const StreamCore& core = cs->core;
+    if (hipMalloc(&cs->ring, (size_t)(core.R + StreamCore::TAIL)) != hipSuccess) rc = LDG_ENOMEM;
+    for (int j = 0; j < core.ncopy && !rc; j++)
+      if (hipStreamCreateWithFlags(&cs->copy[j], hipStreamNonBlocking) != hipSuccess) rc = LDG_EDEVICE;
+    for (int k = 0; k < CapStream::NSTG && !rc; k++)
+      if (hipHostMalloc((void**)&cs->stg[k], (size_t)core.chunk, hipHostMallocDefault) != hipSuccess ||
+          hipEventCreateWithFlags(&cs->ev_stg[k], hipEventDisableTiming) != hipSuccess)
+        rc = LDG_ENOMEM;
+    cs->ev_chunk.assign((size_t)(core.R / core.chunk), nullptr);
+    for (auto& e : cs->ev_chunk)
+      if (!rc && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) rc = LDG_EDEVICE;
+    for (int i = 0; i < StreamCore::NREL && !rc; i++)
+      for (auto& e : cs->ev_rel[i])
+        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) rc = LDG_EDEVICE;
+    if (!rc && ctx->cap_owned) {                      // the streamed capture replaces a resident one
+      dfree(ctx->cap);
+      ctx->cap = nullptr;
+      ctx->cap_alloc = 0;
+      ctx->cap_owned = false;
+    }
   }
-  if (!rc && ctx->cap_owned) {                      // the streamed capture replaces a resident one
-    dfree(ctx->cap);
-    ctx->cap_owned = false;
-  }
+  cs->fd = fd;
+  cs->core.set_file(st.st_size, fmt);
   if (!rc) {
     ctx->cs = cs;
     ctx->fmt = fmt;
     rc = stream_restart(ctx, cs, first_sample);
-    if (!rc) {
-      ctx->cap = cs->ring;
-      ctx->cap_ring = cs->R;
-      ctx->cap_first = cs->sample_ceil(cs->base_b);
-      ctx->cap_nsamp = 0;
-      return LDG_OK;
-    }
-    ctx->cs = nullptr;
   }
+  if (!rc) {
+    stream_attach(ctx, cs, cs->core.sample_ceil(cs->core.base_b), 0);
+    return LDG_OK;
+  }
+  // no stream without a reader is left behind: the next launch would wait for it
   if (rc == LDG_ENOMEM) ctx->err = "stream: out of memory for the ring or its staging";
   stream_free(ctx, cs);
+  ctx->cs = nullptr;
   return rc;
 }
 
 int ldg_stream_release(ldg_ctx* ctx, int64_t below_sample) {
   if (!ctx || !ctx->cs) return LDG_ESTATE;
   CapStream* cs = ctx->cs;
-  const int64_t b = cs->byte_of(std::max<int64_t>(0, std::min(below_sample, cs->total_nsamp)));
-  std::lock_guard<std::mutex> lk(cs->mu);
-  if (b <= cs->release_b) return LDG_OK;
-  int idx;
-  if (!cs->rel_free.empty()) {
-    idx = cs->rel_free.back();
-    cs->rel_free.pop_back();
-    cs->rel.push_back({b, idx});
-  } else {
-    cs->rel.back().first = b;                       // out of records: the newest covers more
-    idx = cs->rel.back().second;
-  }
+  const int64_t b = cs->core.release_byte(below_sample);
+  std::lock_guard<std::mutex> lk(cs->core.mu);
+  const int idx = cs->core.release_pick_locked(b);
+  if (idx < 0) return LDG_OK;
   LDG_TRY(hipEventRecord(cs->ev_rel[idx][0], ctx->stream));
   LDG_TRY(hipEventRecord(cs->ev_rel[idx][1], ctx->stream_b));
-  cs->release_b = b;
-  cs->cv.notify_all();
+  cs->core.release_commit_locked(b);
   return LDG_OK;
 }
 
@@ -443,31 +244,19 @@ int ldg_stream_seek(ldg_ctx* ctx, int64_t first_sample) {
     return LDG_ESTATE;
   }
   LDG_TRY(hipSetDevice(ctx->device));
-  ctx->cs->seeks++;
+  ctx->cs->core.seeks++;
   return stream_restart(ctx, ctx->cs, first_sample);
 }
 
 int ldg_stream_window(ldg_ctx* ctx, int64_t* out4) {
   if (!ctx || !ctx->cs || !out4) return LDG_ESTATE;
-  CapStream* cs = ctx->cs;
-  std::lock_guard<std::mutex> lk(cs->mu);
-  out4[0] = cs->sample_ceil(cs->release_b);                         // lowest sample a launch may read
-  out4[1] = cs->reach_b() / cs->bpg * cs->spg;                      // ... and the highest block end
-  out4[2] = cs->fed_b / cs->bpg * cs->spg;                            // samples queued so far
-  out4[3] = cs->total_nsamp;
+  ctx->cs->core.window(out4);
   return LDG_OK;
 }
 
 int ldg_stream_stats(ldg_ctx* ctx, double* out, int n) {
   if (!ctx || !ctx->cs || !out || n <= 0) return LDG_ESTATE;
-  CapStream* cs = ctx->cs;
-  std::lock_guard<std::mutex> lk(cs->mu);
-  const double v[] = {(double)cs->bytes_read, cs->read_s,        (double)cs->chunks, (double)cs->launch_waits,
-                      cs->launch_wait_s,      cs->space_wait_s,  (double)cs->seeks,  (double)cs->R,
-                      (double)cs->chunk,      cs->stage_wait_s};
-  const int m = std::min<int>(n, (int)(sizeof(v) / sizeof(v[0])));
-  for (int i = 0; i < m; i++) out[i] = v[i];
-  return m;
+  return ctx->cs->core.stats(out, n);
 }
 
 int ldg_stream_close(ldg_ctx* ctx) {
