@@ -270,6 +270,44 @@ int ldg_audio_offsets(double o0, int64_t n, const double* linecounts, double lin
 int ldg_assemble_frames(ldg_ctx* ctx, int n, const int32_t* top_slots, const int32_t* bottom_slots,
                         uint16_t* out, int out_is_device);
 
+/* ---- RF dropouts (BUILD-DEFINED: the reference snapshot has none) ----
+ * Detection, per valid field and picture row r: the samples demod[int(begin) .. int(end))
+ * between the row's two final line locations are flagged when outside [lo_ire, hi_ire]
+ * (or NaN); flagged samples at most merge_gap apart form a run, runs of fewer than
+ * min_flagged flagged samples are dropped, the rest are padded by `pad` samples within the
+ * row and become [startx, endx) pixel runs of the .tbc row, at most
+ * LDG_MAX_DROPOUTS_PER_LINE per row.  Concealment (conceal != 0) replaces each run of the
+ * assembled frame by the same pixels of a nearby row of the same field with the same
+ * chroma phase (r -+ 2, r -+ 4 NTSC; r -+ 4, r -+ 8 PAL) that has no run there; field rows
+ * below LDG_CONCEAL_FIRST_ROW (the VBI) are neither written nor read. */
+#define LDG_MAX_DROPOUTS_PER_LINE 8
+#define LDG_CONCEAL_FIRST_ROW_NTSC 21
+#define LDG_CONCEAL_FIRST_ROW_PAL 22
+#define LDG_CONCEAL_FIRST_ROW(system) ((system) == LDG_SYSTEM_PAL ? LDG_CONCEAL_FIRST_ROW_PAL : LDG_CONCEAL_FIRST_ROW_NTSC)
+typedef struct ldg_dropout_opts {
+  double lo_ire, hi_ire; /* samples outside [lo_ire, hi_ire] are flagged       */
+  int32_t merge_gap;     /* flagged samples this close belong to one run (>= 1) */
+  int32_t min_flagged;   /* flagged samples a run needs                         */
+  int32_t pad;           /* samples added at both ends of a kept run            */
+  int32_t conceal;       /* != 0: frame assembly conceals the runs              */
+} ldg_dropout_opts;
+typedef struct ldg_dropout {
+  int16_t row, startx, endx, pad_; /* field row, pixels [startx, endx) */
+} ldg_dropout;
+/* The defaults: lo_ire = vsync_ire - 50, hi_ire = 150, merge_gap 80, min_flagged 3,
+ * pad 24, conceal 0. */
+int ldg_dropout_defaults(int system, ldg_dropout_opts* out);
+/* NULL: off (the state after ldg_create).  With conceal != 0 every call that assembles
+ * frames (ldg_assemble_frames, ldg_output_async) detects its fields' runs and conceals
+ * the frames in HBM before the comb or any copy; a slot's .tbc lines are not modified. */
+int ldg_set_dropout_opts(ldg_ctx* ctx, const ldg_dropout_opts* opts);
+/* Detect the runs of n live slots: field i's runs in (row, startx) order at
+ * out + i * out_stride (elements), counts[i] of them, -1 for a field that is not valid.
+ * LDG_ESTATE when the options are off, LDG_EINVAL when out_stride is too small for a
+ * field's runs (out_stride >= 8 * 320 always holds them). */
+int ldg_field_dropouts(ldg_ctx* ctx, int n, const int32_t* slots, ldg_dropout* out, int64_t out_stride,
+                       int32_t* counts);
+
 /* Debug / parity access to the per-read device arrays of a live slot.
  * what: 0..4 demod channels (demod, demod_05, demod_sync, demod_burst, demod_pilot)
  *       [float64, n_out] (demod_05, demod_sync and demod_burst are expanded on request from
@@ -277,7 +315,9 @@ int ldg_assemble_frames(ldg_ctx* ctx, int n, const int32_t* top_slots, const int
  *       20..24: linelocs1, linelocs2, linelocs3, linelocs4, final linelocs [float64];
  *       30: burstlevel [float32]; 31: linebad [int8]; 40: dspicture [uint16]; 41: peaklist [int32];
  *       50: the last ldg_comb_ntsc[3d] call's burst-level EMA per line (lines 38..524 of each
- *       frame) [float64]; 51: the comb's carried EMA state [float64] (50 and 51 ignore `slot`).
+ *       frame) [float64]; 51: the comb's carried EMA state [float64] (50 and 51 ignore `slot`);
+ *       60: the slot's raw dropout runs as the last ldg_field_dropouts over it left them
+ *       [int16, 320 rows x 8 x (startx, endx)]; 61: their per-row counts [int32, 320].
  * Copies up to `cap` bytes to host `dst`; returns bytes copied (>= 0) or an error. */
 int64_t ldg_debug_read(ldg_ctx* ctx, int slot, int what, void* dst, int64_t cap);
 

@@ -211,6 +211,16 @@ struct ldg_ctx {
   bool comb_unfused = false;       // LDG_COMB_UNFUSED=1: the default 2D comb as three kernels (split, iq, out)
   int comb_iqw = 28;               // ldg_k_comb_fused's FilterIQ exact warm-up after its scan seed (LDG_COMB_IQW, tests)
   int64_t video_cut = 0;           // ldg_set_video_cut: reads' video cut (0: none)
+  // RF dropouts (dropout.hip; ldg_set_dropout_opts), allocated when first switched on.
+  // Per read slot: what ldg_field_dropouts detects (on sout).  Per field of a frame being
+  // assembled (entry 2 f + parity): what the assembly detects and conceals (on stream2).
+  bool drop_on = false;
+  bool frames_demod = false;       // an assembly has read its slots' demod channel (conceal): the demod waits for ev_frames too
+  ldg_dropout_opts drop_opts{};
+  int16_t *d_drop_runs = nullptr, *d_fdrop_runs = nullptr;
+  int32_t *d_drop_cnt = nullptr, *d_drop_rows = nullptr, *d_fdrop_cnt = nullptr, *d_fdrop_rows = nullptr;
+  int32_t *d_drop_map = nullptr, *d_fdrop_map = nullptr;
+  char* h_drop = nullptr;          // pinned: the slots' runs, counts and line counts for the host
   int comb_rows_wg = 0;            // LDG_COMB_ROWS=G: ldg_k_comb_rows on a persistent grid of G (slower: r04_n)
   bool final_hoist = false;        // LDG_FINAL_HOIST=1: ldg_k_final_lines_h (knot loads with the solve's)
   hipStream_t comb_stream() const { return comb_s2 ? stream2 : scomb; }
@@ -776,6 +786,10 @@ int ldg_destroy(ldg_ctx* ctx) {
                 ctx->d_pcm, ctx->d_counts, ctx->d_next, ctx->d_aerr, ctx->d_frames, ctx->d_frames_b};
   for (void* p : ps) dfree(p);
   for (double2* t : ctx->rf_tab) dfree(t);
+  for (void* p : {(void*)ctx->d_drop_runs, (void*)ctx->d_fdrop_runs, (void*)ctx->d_drop_cnt, (void*)ctx->d_drop_rows,
+                  (void*)ctx->d_fdrop_cnt, (void*)ctx->d_fdrop_rows, (void*)ctx->d_drop_map, (void*)ctx->d_fdrop_map})
+    dfree(p);
+  if (ctx->h_drop) (void)hipHostFree(ctx->h_drop);
   if (ctx->cap_owned) dfree(ctx->cap);
 
   for (void* p : {(void*)ctx->comb_state, (void*)ctx->comb_abl, (void*)ctx->comb_in, (void*)ctx->comb_rgb,
@@ -1219,6 +1233,9 @@ int ldg_decode_reads_async2(ldg_ctx* ctx, int n, const int64_t* read_starts, con
   if (int rc = check_launch(ctx, "ldg_k_rf_table")) return rc;
   LDG_TRY(hipEventRecord(call.ev_prep, sp));
   LDG_TRY(hipStreamWaitEvent(s, call.ev_prep, 0));
+  // with concealment the last frame assembly also read its slots' demod channel
+  // (ldg_k_dropout_lines), which this call's demod rewrites in the slots it reuses
+  if (ctx->frames_recorded && ctx->frames_demod) LDG_TRY(hipStreamWaitEvent(s, ctx->ev_frames, 0));
   hp_.mark("prep");
   if (np && (ctx->stages & 1)) {
     // the probes, then the reads they move, on the demod stream ahead of the demod
@@ -1588,6 +1605,142 @@ int ldg_archive_audio(ldg_ctx* ctx, int n, const int64_t* entries, const double*
   return audio_out(ctx, s, n, pcm, pcm_stride, counts, next_offsets);
 }
 
+// ---- RF dropouts (dropout.hip; build-defined, DESIGN.md section 7) ----------------
+int ldg_dropout_defaults(int system, ldg_dropout_opts* out) {
+  if (!out || (system != LDG_SYSTEM_NTSC && system != LDG_SYSTEM_PAL)) return LDG_EINVAL;
+  const double vsync_ire = system == LDG_SYSTEM_PAL ? -.3 * (100 / .7) : -40.0;
+  out->lo_ire = vsync_ire - 50;
+  out->hi_ire = 150;
+  out->merge_gap = 80;
+  out->min_flagged = 3;
+  out->pad = 24;
+  out->conceal = 0;
+  return LDG_OK;
+}
+
+static int drop_alloc(ldg_ctx* ctx) {
+  if (ctx->d_drop_runs) return LDG_OK;
+  const size_t R = (size_t)ctx->max_reads, F = 2 * (size_t)ctx->max_frames;
+  int rc = 0;
+  rc |= dmalloc(ctx, &ctx->d_drop_cnt, R * MAX_LINES);
+  rc |= dmalloc(ctx, &ctx->d_drop_rows, R);
+  rc |= dmalloc(ctx, &ctx->d_drop_map, R);
+  rc |= dmalloc(ctx, &ctx->d_fdrop_runs, F * DROP_RUNS_STRIDE);
+  rc |= dmalloc(ctx, &ctx->d_fdrop_cnt, F * MAX_LINES);
+  rc |= dmalloc(ctx, &ctx->d_fdrop_rows, F);
+  rc |= dmalloc(ctx, &ctx->d_fdrop_map, F);
+  if (!rc && hipHostMalloc((void**)&ctx->h_drop, R * (DROP_RUNS_STRIDE * sizeof(int16_t) + (MAX_LINES + 1) * sizeof(int32_t)),
+                           hipHostMallocDefault) != hipSuccess)
+    rc |= LDG_ENOMEM;
+  rc |= dmalloc(ctx, &ctx->d_drop_runs, R * DROP_RUNS_STRIDE);     // last: marks the set complete
+  if (rc) {
+    for (void** p : {(void**)&ctx->d_drop_runs, (void**)&ctx->d_fdrop_runs, (void**)&ctx->d_drop_cnt, (void**)&ctx->d_drop_rows,
+                     (void**)&ctx->d_fdrop_cnt, (void**)&ctx->d_fdrop_rows, (void**)&ctx->d_drop_map, (void**)&ctx->d_fdrop_map}) {
+      dfree(*p);
+      *p = nullptr;
+    }
+    if (ctx->h_drop) (void)hipHostFree(ctx->h_drop);
+    ctx->h_drop = nullptr;
+    ctx->err = "dropout buffers: out of memory";
+    return LDG_ENOMEM;
+  }
+  // a slot never detected reads as "not valid", its rows as empty
+  LDG_TRY(hipMemset(ctx->d_drop_rows, 0xff, R * sizeof(int32_t)));
+  LDG_TRY(hipMemset(ctx->d_drop_cnt, 0, R * MAX_LINES * sizeof(int32_t)));
+  LDG_TRY(hipMemset(ctx->d_drop_runs, 0, R * DROP_RUNS_STRIDE * sizeof(int16_t)));
+  return LDG_OK;
+}
+
+int ldg_set_dropout_opts(ldg_ctx* ctx, const ldg_dropout_opts* o) {
+  if (!ctx) return LDG_EINVAL;
+  if (!o) {
+    ctx->drop_on = false;
+    return LDG_OK;
+  }
+  if (!(o->lo_ire <= o->hi_ire) || o->merge_gap < 1 || o->merge_gap > (1 << 20) || o->min_flagged < 1 || o->pad < 0 ||
+      o->pad > (1 << 20)) {
+    ctx->err = "ldg_set_dropout_opts: lo_ire <= hi_ire, merge_gap >= 1, min_flagged >= 1, pad >= 0";
+    return LDG_EINVAL;
+  }
+  LDG_TRY(hipSetDevice(ctx->device));
+  if (int rc = drop_alloc(ctx)) return rc;
+  ctx->drop_opts = *o;
+  ctx->drop_on = true;
+  return LDG_OK;
+}
+
+// ldg_k_dropout_lines over n slots (device map) on stream s
+static int drop_detect(ldg_ctx* ctx, hipStream_t s, int n, const int32_t* d_map, int by_slot, int16_t* runs,
+                       int32_t* counts, int32_t* nrows) {
+  const SysConst& C = ctx->C;
+  DropParams P;
+  P.lo_hz = C.ire0 + C.hz_ire * ctx->drop_opts.lo_ire;
+  P.hi_hz = C.ire0 + C.hz_ire * ctx->drop_opts.hi_ire;
+  P.merge_gap = ctx->drop_opts.merge_gap;
+  P.min_flagged = ctx->drop_opts.min_flagged;
+  P.pad = ctx->drop_opts.pad;
+  P.pad_ = 0;
+  const dim3 g_rows((unsigned)(C.frame_lines / 2 + 1), (unsigned)n);     // as ldg_k_final_lines
+  LDG_LAUNCH_ON(s, "dropout_lines", ldg_k_dropout_lines, g_rows, 64, d_map, by_slot, ctx->video, ctx->vread, ctx->vchan,
+                C, ctx->d_recs, ctx->d_lines, P, runs, counts, nrows);
+  return check_launch(ctx, "ldg_k_dropout_lines");
+}
+
+int ldg_field_dropouts(ldg_ctx* ctx, int n, const int32_t* slots, ldg_dropout* out, int64_t out_stride,
+                       int32_t* counts) {
+  if (!ctx || n < 0 || n > ctx->max_reads || (n && (!slots || !out || !counts)) || out_stride < 0) return LDG_EINVAL;
+  if (!ctx->drop_on) {
+    ctx->err = "ldg_field_dropouts: the dropout options are off (ldg_set_dropout_opts)";
+    return LDG_ESTATE;
+  }
+  if (n == 0) return LDG_OK;
+  int lo = ctx->max_reads, hi = -1;
+  for (int i = 0; i < n; i++) {
+    if (slots[i] < 0 || slots[i] >= ctx->max_reads || !ctx->live[slots[i]]) return LDG_EINVAL;
+    lo = std::min(lo, (int)slots[i]);
+    hi = std::max(hi, (int)slots[i]);
+  }
+  LDG_TRY(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->sout;     // output work: overlaps the outstanding decodes
+  if (int rc = stage_h2d(ctx, ctx->d_drop_map, slots, n * sizeof(int32_t), s)) return rc;
+  if (int rc = drop_detect(ctx, s, n, ctx->d_drop_map, 1, ctx->d_drop_runs, ctx->d_drop_cnt, ctx->d_drop_rows)) return rc;
+  // the slots' span of the three arrays in one copy each
+  const size_t m = (size_t)(hi - lo + 1);
+  int16_t* h_runs = (int16_t*)ctx->h_drop;
+  int32_t* h_cnt = (int32_t*)(h_runs + (size_t)ctx->max_reads * DROP_RUNS_STRIDE);
+  int32_t* h_rows = h_cnt + (size_t)ctx->max_reads * MAX_LINES;
+  LDG_TRY(hipMemcpyAsync(h_runs, ctx->d_drop_runs + (size_t)lo * DROP_RUNS_STRIDE, m * DROP_RUNS_STRIDE * sizeof(int16_t),
+                         hipMemcpyDeviceToHost, s));
+  LDG_TRY(hipMemcpyAsync(h_cnt, ctx->d_drop_cnt + (size_t)lo * MAX_LINES, m * MAX_LINES * sizeof(int32_t),
+                         hipMemcpyDeviceToHost, s));
+  LDG_TRY(hipMemcpyAsync(h_rows, ctx->d_drop_rows + lo, m * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  LDG_TRY(hipStreamSynchronize(s));
+  prof_collect(ctx);
+  for (int i = 0; i < n; i++) {
+    const size_t e = (size_t)(slots[i] - lo);
+    const int rows = h_rows[e];
+    if (rows < 0) {
+      counts[i] = -1;
+      continue;
+    }
+    ldg_dropout* o = out + (size_t)i * out_stride;
+    int64_t k = 0;
+    for (int r = 0; r < rows && r < MAX_LINES; r++) {
+      const int c = std::min<int>(std::max<int>(h_cnt[e * MAX_LINES + r], 0), MAX_DROPOUTS);
+      for (int q = 0; q < c; q++) {
+        if (k >= out_stride) {
+          ctx->err = "ldg_field_dropouts: out_stride is too small for a field's runs";
+          return LDG_EINVAL;
+        }
+        const int16_t* p = h_runs + e * DROP_RUNS_STRIDE + ((size_t)r * MAX_DROPOUTS + q) * 2;
+        o[k++] = ldg_dropout{(int16_t)r, p[0], p[1], 0};
+      }
+    }
+    counts[i] = (int32_t)k;
+  }
+  return LDG_OK;
+}
+
 int ldg_assemble_frames(ldg_ctx* ctx, int n, const int32_t* top_slots, const int32_t* bottom_slots, uint16_t* out,
                         int out_is_device) {
   // out == NULL with out_is_device: frames stay in the context's internal device frame buffer
@@ -1610,13 +1763,32 @@ int ldg_assemble_frames(ldg_ctx* ctx, int n, const int32_t* top_slots, const int
     if (ctx->fbuf_recorded[ctx->fb]) LDG_TRY(hipStreamWaitEvent(s, ctx->ev_fbuf[ctx->fb], 0));
     dst = ctx->frame_buf(ctx->fb);
   }
+  const bool conceal = ctx->drop_on && ctx->drop_opts.conceal;
+  if (conceal) {
+    // the fields' runs (entry 2 f + parity), while their slots are still protected
+    std::vector<int32_t> map(2 * (size_t)n);
+    for (int i = 0; i < n; i++) {
+      map[2 * i] = top_slots[i];
+      map[2 * i + 1] = bottom_slots[i];
+    }
+    if (int rc = stage_h2d(ctx, ctx->d_fdrop_map, map.data(), map.size() * sizeof(int32_t), s)) return rc;
+    if (int rc = drop_detect(ctx, s, 2 * n, ctx->d_fdrop_map, 0, ctx->d_fdrop_runs, ctx->d_fdrop_cnt, ctx->d_fdrop_rows))
+      return rc;
+  }
   dim3 grid(n, (ctx->C.frame_lines + FRAME_ROWS - 1) / FRAME_ROWS);
   LDG_LAUNCH_ON(s, "frames", ldg_k_frames, grid, 256, ctx->d_slots, ctx->d_slots2, ctx->d_recs, ctx->d_pic,
              ctx->pic_stride, ctx->C, dst);
   if (int rc = check_launch(ctx, "ldg_k_frames")) return rc;
+  if (conceal) {
+    // in place, before the comb or any copy sees the frames (both wait for ev_frames / this stream)
+    LDG_LAUNCH_ON(s, "conceal", ldg_k_conceal, dim3((unsigned)ctx->C.frame_lines, (unsigned)n), 64, ctx->d_fdrop_runs,
+                  ctx->d_fdrop_cnt, ctx->d_fdrop_rows, ctx->C, dst);
+    if (int rc = check_launch(ctx, "ldg_k_conceal")) return rc;
+  }
   // the next decode's field chains (which rewrite slots) wait for this
   LDG_TRY(hipEventRecord(ctx->ev_frames, s));
   ctx->frames_recorded = true;
+  if (conceal) ctx->frames_demod = true;
   if (out_is_device) return LDG_OK;      // stays queued on the output stream
   LDG_TRY(hipMemcpyAsync(out, dst, n * fsz * sizeof(uint16_t), hipMemcpyDeviceToHost, s));
   LDG_TRY(hipStreamSynchronize(s));
@@ -2325,6 +2497,13 @@ int64_t ldg_debug_read(ldg_ctx* ctx, int slot, int what, void* dst, int64_t cap)
   } else if (what == 41) {
     src = ctx->d_peaks + (int64_t)slot * MAX_PEAKS;
     bytes = (int64_t)MAX_PEAKS * 4;
+  } else if (what == 60 || what == 61) {
+    // the slot's dropout runs / per-row counts as the last ldg_field_dropouts left them
+    if (!ctx->d_drop_runs) return LDG_EINVAL;
+    if (hipStreamSynchronize(ctx->sout) != hipSuccess) return LDG_EDEVICE;
+    src = what == 60 ? (const void*)(ctx->d_drop_runs + (int64_t)slot * DROP_RUNS_STRIDE)
+                     : (const void*)(ctx->d_drop_cnt + (int64_t)slot * MAX_LINES);
+    bytes = what == 60 ? (int64_t)DROP_RUNS_STRIDE * 2 : (int64_t)MAX_LINES * 4;
   } else {
     return LDG_EINVAL;
   }

@@ -109,6 +109,16 @@ def parse(argv=None):
     p.add_argument('--comb-args', default='',
                    help="comb-ntsc options for --comb (NTSC), e.g. '-I 0 -N 1 -v' (comb_ntsc.py's -I -b -n -N "
                         "-B -a -L -Q -v -l -W)")
+    p.add_argument('--dropouts', action='store_true',
+                   help="detect RF dropouts (build-defined rule, DESIGN.md section 7): every valid field's record in "
+                        "<outfile>.json gets 'dropouts': [[row, startx, endx], ...]")
+    p.add_argument('--conceal', action='store_true',
+                   help='implies --dropouts: replace each dropout in the .tbc frames (and what the comb sees) by the '
+                        'same pixels of a nearby line of the same field with the same chroma phase')
+    p.add_argument('--dropout-lo-ire', type=float, default=None,
+                   help='samples below this level are flagged (default: the sync tip - 50 IRE)')
+    p.add_argument('--dropout-hi-ire', type=float, default=None,
+                   help='samples above this level are flagged (default 150 IRE)')
     p.add_argument('--no-json', action='store_true', help='do not write <outfile>.json')
     p.add_argument('--stats-json', default=None,
                    help='one process: write a timing breakdown of the run (read, decode, write) to this file')
@@ -164,7 +174,17 @@ def main(argv=None):
             print("ERROR: a sharded decode runs the 2D / 3D (-F) comb (NTSC) or the PAL Y/C decoder: the optical "
                   "flow's estimate chains over every frame")
             return 1
-    dec = GPUDecoder(system=system, device=args.device, batch=args.batch)
+    dropouts = None
+    if args.conceal or args.dropouts or args.dropout_lo_ire is not None or args.dropout_hi_ire is not None:
+        if args.cut:
+            print("ERROR: --dropouts / --conceal apply to a decode, not to -c (cut)")
+            return 1
+        dropouts = {'conceal': int(args.conceal)}
+        if args.dropout_lo_ire is not None:
+            dropouts['lo_ire'] = args.dropout_lo_ire
+        if args.dropout_hi_ire is not None:
+            dropouts['hi_ire'] = args.dropout_hi_ire
+    dec = GPUDecoder(system=system, device=args.device, batch=args.batch, dropouts=dropouts)
     if args.comb_args:
         import shlex
         import comb_ntsc
@@ -415,11 +435,13 @@ def sharded(args, dec, outname, firstframe, num_frames, nextsample, req_frames, 
              'exts': list(exts), 'num_frames': num_frames, 'firstframe': firstframe, 'seek': args.seek,
              'start_sample': int(nextsample), 'system': dec.sysp.name, 'comb': bool(args.comb),
              'comb_args': args.comb_args, 'no_json': bool(args.no_json)}
+    if dec.dropouts is not None:               # (absent when off: the manifest of a plain decode is unchanged)
+        ident['dropouts'] = dec.dropouts
     man = None
     if args.manifest and os.path.exists(args.manifest):
         with open(args.manifest) as fh:
             man = json.load(fh)
-        if any(man.get(k) != v for k, v in ident.items()):
+        if any(man.get(k) != v for k, v in ident.items()) or man.get('dropouts') != dec.dropouts:
             print('ERROR: %s belongs to another decode' % args.manifest)
             return 1
         if man.get('complete'):

@@ -219,7 +219,7 @@ class GPUDecoder:
     plan_guessed = full_keys = frozenset()
     _hint_keys = ()
 
-    def __init__(self, system='NTSC', device=0, batch=32, capacity=None, log=None):
+    def __init__(self, system='NTSC', device=0, batch=32, capacity=None, log=None, dropouts=None):
         self.rf = RFTables(system)
         self.sysp = self.rf.system
         self.batch = batch
@@ -289,6 +289,10 @@ class GPUDecoder:
         self.video_cut = int(vc) if vc is not None else (740000 if self.sysp.name == 'NTSC' else 880000)
         self.full_keys = set()
         self.ctx.set_video_cut(self.video_cut)
+        # RF dropouts (build-defined): None = off; a dict of ldg_dropout_opts
+        # fields over the defaults ({} = the defaults) detects every output field's runs
+        # (the records' 'dropouts' key) and, with conceal, conceals them in the frames
+        self.dropouts = self.ctx.set_dropout_opts(dict(dropouts)) if dropouts is not None else None
         self.plan_located = 0              # leading fields the last plan walked on decoded reads
         self.htrace = [] if os.environ.get('LDG_HOSTTRACE') else None   # (perf_counter, event, n): host timeline
         self.comb, self.comb_sink = False, None
@@ -1160,6 +1164,15 @@ class GPUDecoder:
             return
         tops = [f.top.slot for f in frames]
         bots = [f.bottom.slot for f in frames]
+        if self.dropouts is not None:
+            # while the batch's slots are still protected: the runs of every valid field these
+            # frames' readframe calls read, into the fields' records
+            objs = [x for fr in frames for x in fr.field_objs if x.valid]
+            runs = iter(self.ctx.field_dropouts([x.slot for x in objs])) if objs else iter(())
+            for fr in frames:
+                for x, rec in zip(fr.field_objs, fr.fields):
+                    if x.valid:
+                        rec['dropouts'] = next(runs).tolist()
         if sink is None:
             # benchmark mode: .tbc frames (and their comb output) stay in HBM
             self.ctx.assemble_frames_device(tops, bots)

@@ -29,7 +29,10 @@ EXPORTS = ['ldg_create', 'ldg_destroy', 'ldg_last_error', 'ldg_set_filters', 'ld
            'ldg_field_audio_async', 'ldg_field_audio_collect', 'ldg_comb_ntsc3d', 'ldg_cx_create', 'ldg_cx_destroy', 'ldg_cx_process', 'ldg_comb_pal', 'ldg_comb_set_state', 'ldg_profile_spans', 'ldg_profile_spans_union', 'ldg_profile_span_table',
            'ldg_audio_offsets', 'ldg_comb_async', 'ldg_debug_rf_table',
            'ldg_stream_open', 'ldg_stream_release', 'ldg_stream_seek', 'ldg_stream_window', 'ldg_stream_stats',
-           'ldg_stream_close', 'ldg_device_memory']
+           'ldg_stream_close', 'ldg_device_memory',
+           'ldg_dropout_defaults', 'ldg_set_dropout_opts', 'ldg_field_dropouts']
+MAX_DROPOUTS_PER_LINE = 8         # LDG_MAX_DROPOUTS_PER_LINE
+MAX_LINES = 320                   # rows of the per-slot line arrays (ldg_debug_read)
 STREAM_STATS = ('bytes_read', 'read_s', 'chunks', 'launch_waits', 'launch_wait_s', 'space_wait_s', 'seeks',
                 'ring_bytes', 'chunk_bytes', 'stage_wait_s')     # ldg_stream_stats, in order
 
@@ -78,6 +81,25 @@ class CombOpts(C.Structure):
                 ('bw', C.c_int32), ('adaptive2d', C.c_int32), ('colorlpf', C.c_int32), ('colorlpf_hq', C.c_int32),
                 ('linesout', C.c_int32), ('debug_line', C.c_int32), ('wide', C.c_int32),
                 ('opticalflow', C.c_int32)]
+
+
+class DropoutOpts(C.Structure):
+    """ldg_dropout_opts (include/ldgpu.h): the build-defined dropout detector's options."""
+    _fields_ = [('lo_ire', C.c_double), ('hi_ire', C.c_double), ('merge_gap', C.c_int32),
+                ('min_flagged', C.c_int32), ('pad', C.c_int32), ('conceal', C.c_int32)]
+
+
+class Dropout(C.Structure):
+    """ldg_dropout: pixels [startx, endx) of field row `row`."""
+    _fields_ = [('row', C.c_int16), ('startx', C.c_int16), ('endx', C.c_int16), ('pad_', C.c_int16)]
+
+
+def dropout_defaults(system):
+    """ldg_dropout_defaults as a dict (keys of ldg_dropout_opts); no device needed."""
+    o = DropoutOpts()
+    if load().ldg_dropout_defaults(1 if system == 'PAL' else 0, C.byref(o)) != LDG_OK:
+        raise LDGError('ldg_dropout_defaults failed')
+    return {k: getattr(o, k) for k, _ in DropoutOpts._fields_}
 
 
 COMB_DEFAULTS = dict(black_ire=7.5, brightness=236.0, nr_y=1.0, nr_c=0.0, bw=False, adaptive2d=True, colorlpf=True,
@@ -170,6 +192,9 @@ def load(path=None):
     lib.ldg_stream_stats.argtypes = [vp, vp, C.c_int]
     lib.ldg_stream_close.argtypes = [vp]
     lib.ldg_device_memory.argtypes = [C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.ldg_dropout_defaults.argtypes = [C.c_int, C.POINTER(DropoutOpts)]
+    lib.ldg_set_dropout_opts.argtypes = [vp, C.POINTER(DropoutOpts)]
+    lib.ldg_field_dropouts.argtypes = [vp, C.c_int, vp, vp, C.c_int64, vp]
     lib.ldg_version.restype = C.c_char_p
     lib.ldg_device_count.restype = C.c_int
     _lib = lib
@@ -551,6 +576,39 @@ class Context:
         self._check(self.lib.ldg_comb_set_opts(self.h, C.byref(c)), 'ldg_comb_set_opts')
         self.comb_lines = int(o['linesout'])
         self.comb_width = 910 if o['wide'] else 744
+
+    # ---- RF dropouts (build-defined; include/ldgpu.h) ---------------------------------
+    def set_dropout_opts(self, opts=None, **kw):
+        """ldg_set_dropout_opts: None switches the feature off; a dict (or keywords) of
+        ldg_dropout_opts fields over the system's defaults switches it on.  Returns the
+        options in force (None: off)."""
+        if opts is None and not kw:
+            self._check(self.lib.ldg_set_dropout_opts(self.h, None), 'ldg_set_dropout_opts')
+            return None
+        o = dropout_defaults(self.system)
+        for k, v in dict(opts or {}, **kw).items():
+            if k not in o:
+                raise TypeError('unknown dropout option %s' % k)
+            o[k] = v
+        c = DropoutOpts(float(o['lo_ire']), float(o['hi_ire']), int(o['merge_gap']), int(o['min_flagged']),
+                        int(o['pad']), int(bool(o['conceal'])))
+        self._check(self.lib.ldg_set_dropout_opts(self.h, C.byref(c)), 'ldg_set_dropout_opts')
+        return o
+
+    def field_dropouts(self, slots):
+        """ldg_field_dropouts: per slot an int16 array [count, 3] of (row, startx, endx) in
+        (row, startx) order, or None for a field that is not valid."""
+        if len(slots) > self.max_reads:               # (a call takes at most max_reads slots)
+            return [r for i in range(0, len(slots), self.max_reads)
+                    for r in self.field_dropouts(slots[i:i + self.max_reads])]
+        n = len(slots)
+        stride = MAX_DROPOUTS_PER_LINE * MAX_LINES
+        out = np.empty((max(n, 1), stride, 4), dtype=np.int16)
+        counts = np.zeros(max(n, 1), dtype=np.int32)
+        sl = np.ascontiguousarray(slots, dtype=np.int32)
+        self._check(self.lib.ldg_field_dropouts(self.h, n, sl.ctypes.data, out.ctypes.data, stride, counts.ctypes.data),
+                    'ldg_field_dropouts')
+        return [None if counts[i] < 0 else out[i, :counts[i], :3].copy() for i in range(n)]
 
     def comb_reset(self):
         self._check(self.lib.ldg_comb_reset(self.h), 'ldg_comb_reset')
