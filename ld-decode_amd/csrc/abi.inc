@@ -77,7 +77,6 @@ struct ldg_ctx {
   int nsub = 2;                    // LDG_DECODE_STREAMS: 8 measured 15x slower (queue oversubscription), 2 ~ 4
   int stages = 7;                  // debug (LDG_STAGES): bit 0 demod, 1 audio phase 2, 2 field chains
   int skip = 0;                    // debug (LDG_SKIP): field-chain kernels not launched (timing probes only)
-  bool demod_split = false;        // LDG_DEMOD_SPLIT: demod group by group, each group's chain after its own
   // demod execution spans while profiling (ldg_profile_spans)
   static constexpr int SPAN_MAX = 8192;
   unsigned long long* d_span = nullptr;
@@ -103,7 +102,6 @@ struct ldg_ctx {
     int n = 0;
     std::vector<int32_t> smap;
     hipEvent_t ev_demod = nullptr;
-    hipEvent_t ev_dg[MAX_SUB] = {};  // split demod: group g's reads are demodulated
     hipEvent_t ev_done[MAX_SUB + 1] = {};
     hipEvent_t ev_copied = nullptr;  // the call's records are in h_recs_pin
     hipEvent_t ev_prep = nullptr;    // the call's slots and rf tables are set up
@@ -205,8 +203,6 @@ struct ldg_ctx {
   uint16_t* d_frames = nullptr;
   uint16_t* d_frames_b = nullptr;
   int fb = 0;
-  bool fbuf_single = false;        // LDG_FBUF1=1: one frame buffer (probe)
-  bool comb_s2 = false;            // LDG_COMB_S2=1: the comb on the output stream (probe)
   bool comb_generic = false;       // LDG_COMB_GENERIC=1: the option-taking comb kernels even at the defaults
   bool comb_unfused = false;       // LDG_COMB_UNFUSED=1: the default 2D comb as three kernels (split, iq, out)
   int comb_iqw = 28;               // ldg_k_comb_fused's FilterIQ exact warm-up after its scan seed (LDG_COMB_IQW, tests)
@@ -221,9 +217,6 @@ struct ldg_ctx {
   int32_t *d_drop_cnt = nullptr, *d_drop_rows = nullptr, *d_fdrop_cnt = nullptr, *d_fdrop_rows = nullptr;
   int32_t *d_drop_map = nullptr, *d_fdrop_map = nullptr;
   char* h_drop = nullptr;          // pinned: the slots' runs, counts and line counts for the host
-  int comb_rows_wg = 0;            // LDG_COMB_ROWS=G: ldg_k_comb_rows on a persistent grid of G (slower: r04_n)
-  bool final_hoist = false;        // LDG_FINAL_HOIST=1: ldg_k_final_lines_h (knot loads with the solve's)
-  hipStream_t comb_stream() const { return comb_s2 ? stream2 : scomb; }
   hipEvent_t ev_fbuf[2] = {nullptr, nullptr};
   bool fbuf_recorded[2] = {false, false};
   hipEvent_t ev_tbc = nullptr;
@@ -516,39 +509,6 @@ int ldg_device_memory(int device, int64_t* free_bytes, int64_t* total_bytes) {
 
 const char* ldg_last_error(const ldg_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 
-// A non-blocking stream; hi: the device's greatest priority.  With LDG_PRIO >= 1
-// (the default) the field chains, read setup and record copies outrank the
-// demod, so their small grids take CUs as the demod's workgroups retire
-// instead of waiting behind its queue (2: the audio stream too).
-// CU partition (LDG_CHAIN_CUS = K > 0, experimental): the demod stream runs on all
-// but K CUs of each XCD and every other stream on those K.  A demod workgroup
-// needs a whole CU (all its VGPRs and most of its LDS), so any field-chain wave
-// on a CU keeps the demod off it; confining the chains packs them onto few CUs.
-// CU-mask bit i = CU i / 8 of XCD i % 8.  LDG_CU_ALL (with LDG_CHAIN_CUS): the
-// stream letters of LDG_STREAM_ORDER that keep every CU (e.g. "Dd": the demod on
-// all CUs, the rest confined to the K CUs).
-static int g_chain_cus = 0;
-static std::string g_cu_all;
-enum StreamRole { ROLE_DEMOD, ROLE_CHAIN };
-static hipError_t make_stream(hipStream_t* st, bool hi, StreamRole role = ROLE_CHAIN, char letter = 0) {
-  if (g_chain_cus > 0 && !(letter && g_cu_all.find(letter) != std::string::npos)) {
-    uint32_t m[8];
-    for (int w = 0; w < 8; w++) {
-      m[w] = 0;
-      for (int b = 0; b < 32; b++) {
-        const int i = 32 * w + b;
-        const bool chain = (i / 8) < g_chain_cus;
-        if (chain == (role == ROLE_CHAIN)) m[w] |= 1u << b;
-      }
-    }
-    return hipExtStreamCreateWithCUMask(st, 8, m);
-  }
-  int lo = 0, top = 0;
-  if (!hi || hipDeviceGetStreamPriorityRange(&lo, &top) != hipSuccess)
-    return hipStreamCreateWithFlags(st, hipStreamNonBlocking);
-  return hipStreamCreateWithPriority(st, hipStreamNonBlocking, top);
-}
-
 int ldg_create(const ldg_config* cfg, ldg_ctx** out) {
   if (!cfg || !out || cfg->max_reads <= 0 || (cfg->system != 0 && cfg->system != 1)) return LDG_EINVAL;
   *out = nullptr;
@@ -562,31 +522,10 @@ int ldg_create(const ldg_config* cfg, ldg_ctx** out) {
     delete ctx;
     return LDG_EDEVICE;
   }
-  // LDG_PRIO (default 0): field-chain streams at top priority.  With four chain
-  // streams it cut the launch period ~4%; with the two of the default it
-  // measured 2% slower (interleaved A/B), and two processes sharing one GPU
-  // with top-priority queues starved each other's work (a 2-rank bench
-  // stalled), so it is opt-in, and never used with more local ranks than GPUs
-  int prio = 0;
-  if (const char* pe = getenv("LDG_PRIO")) prio = atoi(pe);
-  if (const char* lw = getenv("LOCAL_WORLD_SIZE")) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || atoi(lw) > ndev) prio = 0;
-  }
-  const bool hi = prio > 0;
-  g_chain_cus = 0;
-  if (const char* e = getenv("LDG_CHAIN_CUS")) g_chain_cus = std::max(0, std::min(31, atoi(e)));
-  g_cu_all.clear();
-  if (const char* e = getenv("LDG_CU_ALL")) g_cu_all = e;
-  // LDG_PRIO = -1 (experimental): the demod stream at top priority instead
   if (const char* e = getenv("LDG_DEMOD_STREAMS")) ctx->demod_streams = atoi(e) == 1 ? 1 : 2;
-  if (const char* e = getenv("LDG_FBUF1")) ctx->fbuf_single = atoi(e) != 0;
-  if (const char* e = getenv("LDG_COMB_S2")) ctx->comb_s2 = atoi(e) != 0;
   if (const char* e = getenv("LDG_COMB_GENERIC")) ctx->comb_generic = atoi(e) != 0;
   if (const char* e = getenv("LDG_COMB_UNFUSED")) ctx->comb_unfused = atoi(e) != 0;
   if (const char* e = getenv("LDG_COMB_IQW")) ctx->comb_iqw = std::max(0, atoi(e));
-  if (const char* e = getenv("LDG_COMB_ROWS")) ctx->comb_rows_wg = std::max(0, atoi(e));
-  if (const char* e = getenv("LDG_FINAL_HOIST")) ctx->final_hoist = atoi(e) != 0;
   if (const char* e = getenv("LDG_COMB_WARM")) ctx->comb_warm = std::max(0, atoi(e));
   if (const char* e = getenv("LDG_DECODE_STREAMS")) ctx->nsub = atoi(e);
   ctx->nsub = ctx->nsub < 1 ? 1 : ctx->nsub > ldg_ctx::MAX_SUB ? ldg_ctx::MAX_SUB : ctx->nsub;
@@ -595,31 +534,17 @@ int ldg_create(const ldg_config* cfg, ldg_ctx** out) {
   // second and third) ran 96.2 ms per 60 s step, the round-2 order (comb last)
   // 94.4, and orders that create the demod and field-chain streams first 91.5 –
   // 92.7 (profiles/r03_k_stream_order.txt).
-  // LDG_STREAM_ORDER (probe): D demod, d second demod, o output, a audio, s audio
-  // out, r records, p read setup, c comb, S the field-chain streams.
-  const std::string kOrder = "DSdaosrpc";
-  std::string order = kOrder;
-  if (const char* e = getenv("LDG_STREAM_ORDER")) order = e;
-  bool made_ok = order.size() == 9;
-  for (char ch : kOrder) made_ok = made_ok && order.find(ch) != std::string::npos;
-  if (!made_ok) order = kOrder;
-  made_ok = true;
-  for (char ch : order) {
-    hipError_t e = hipSuccess;
-    switch (ch) {
-      case 'D': e = make_stream(&ctx->stream, prio < 0, ROLE_DEMOD, 'D'); break;
-      case 'd': e = make_stream(&ctx->stream_b, prio < 0, ROLE_DEMOD, 'd'); break;
-      case 'o': e = make_stream(&ctx->stream2, false, ROLE_CHAIN, 'o'); break;
-      case 'a': e = make_stream(&ctx->sa, prio > 1, ROLE_CHAIN, 'a'); break;
-      case 's': e = make_stream(&ctx->sout, false, ROLE_CHAIN, 's'); break;
-      case 'r': e = make_stream(&ctx->srec, hi, ROLE_CHAIN, 'r'); break;
-      case 'p': e = make_stream(&ctx->sprep, hi, ROLE_CHAIN, 'p'); break;
-      case 'c': e = make_stream(&ctx->scomb, false, ROLE_CHAIN, 'c'); break;
-      default:
-        for (int k = 0; k < ctx->nsub && e == hipSuccess; k++) e = make_stream(&ctx->sub[k], hi, ROLE_CHAIN, 'S');
-    }
-    if (e != hipSuccess) made_ok = false;
-  }
+  bool made_ok = true;
+  auto make = [&](hipStream_t* st) { made_ok &= hipStreamCreateWithFlags(st, hipStreamNonBlocking) == hipSuccess; };
+  make(&ctx->stream);                                        // D demod
+  for (int k = 0; k < ctx->nsub; k++) make(&ctx->sub[k]);    // S the field-chain streams
+  make(&ctx->stream_b);                                      // d second demod
+  make(&ctx->sa);                                            // a audio
+  make(&ctx->stream2);                                       // o output
+  make(&ctx->sout);                                          // s audio out
+  make(&ctx->srec);                                          // r records
+  make(&ctx->sprep);                                         // p read setup
+  make(&ctx->scomb);                                         // c comb
   if (!made_ok ||
       hipEventCreateWithFlags(&ctx->ev_fbuf[0], hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&ctx->ev_fbuf[1], hipEventDisableTiming) != hipSuccess ||
@@ -641,11 +566,6 @@ int ldg_create(const ldg_config* cfg, ldg_ctx** out) {
       return LDG_EDEVICE;
     }
   for (auto& c : ctx->calls) {
-    for (auto& e : c.ev_dg)
-      if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
-        ldg_destroy(ctx);
-        return LDG_EDEVICE;
-      }
     if (hipEventCreateWithFlags(&c.ev_demod, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c.ev_copied, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c.ev_prep, hipEventDisableTiming) != hipSuccess) {
@@ -758,8 +678,6 @@ int ldg_destroy(ldg_ctx* ctx) {
     }
   for (auto& c : ctx->calls) {
     if (c.ev_demod) (void)hipEventDestroy(c.ev_demod);
-    for (auto e : c.ev_dg)
-      if (e) (void)hipEventDestroy(e);
     if (c.ev_copied) (void)hipEventDestroy(c.ev_copied);
     if (c.ev_prep) (void)hipEventDestroy(c.ev_prep);
     for (auto e : c.ev_done)
@@ -1002,19 +920,20 @@ static unsigned long long* span_slot(ldg_ctx* ctx) {
   return ctx->d_span + 2 * (size_t)ctx->span_n++;
 }
 
-// The per-read kernel chain (demod -> sync -> line locations -> TBC) for n reads
-// whose slots are M_[0..n), on stream st; ospill: the demod's park for this group.
-static int launch_reads(ldg_ctx* ctx, hipStream_t st, int n, const int32_t* M_, double2* ospill, bool demod,
-                        bool fields) {
+// The demod of the n reads whose slots are M_[0..n), on stream st.
+static int launch_demod(ldg_ctx* ctx, hipStream_t st, int n, const int32_t* M_) {
   const SysConst C = ctx->C;
-  if (demod) {
-    LDG_LAUNCH_ON(st, "demod", ldg_k_demod, n * MAX_BLOCKS_PER_READ, 1024, M_, ctx->d_reads, ctx->cap, ctx->cap_first,
-               ctx->cap_nsamp, ctx->cap_ring, ctx->fmt, ctx->tw, ctx->twk, ctx->rf_cur, ctx->fvideo, ctx->f05, ctx->iirtab, ctx->alf, ctx->arf, C, ctx->video, ctx->vread, ctx->vchan, ctx->audio1, ctx->a1read,
-               ctx->a1chan, ctx->d_status, ospill, ++ctx->park_epoch, ctx->d_stile, ctx->d_aslice,
-               ctx->d_sst, ctx->d_sbits, ctx->d_bst, span_slot(ctx));
-    if (int rc = check_launch(ctx, "ldg_k_demod")) return rc;
-  }
-  if (!fields) return LDG_OK;
+  LDG_LAUNCH_ON(st, "demod", ldg_k_demod, n * MAX_BLOCKS_PER_READ, 1024, M_, ctx->d_reads, ctx->cap, ctx->cap_first,
+             ctx->cap_nsamp, ctx->cap_ring, ctx->fmt, ctx->tw, ctx->twk, ctx->rf_cur, ctx->fvideo, ctx->f05, ctx->iirtab, ctx->alf, ctx->arf, C, ctx->video, ctx->vread, ctx->vchan, ctx->audio1, ctx->a1read,
+             ctx->a1chan, ctx->d_status, ctx->d_ospill, ++ctx->park_epoch, ctx->d_stile, ctx->d_aslice,
+             ctx->d_sst, ctx->d_sbits, ctx->d_bst, span_slot(ctx));
+  return check_launch(ctx, "ldg_k_demod");
+}
+
+// The per-read field kernel chain (sync -> line locations -> TBC) for n demodulated
+// reads whose slots are M_[0..n), on stream st.
+static int launch_chain(ldg_ctx* ctx, hipStream_t st, int n, const int32_t* M_) {
+  const SysConst C = ctx->C;
   if (!(ctx->skip >> 0 & 1)) LDG_LAUNCH_ON(st, "sync_walk", ldg_k_sync_walk, n * SEG_K, 64, M_, ctx->d_reads, ctx->video, ctx->vread, ctx->vchan, C,
              ctx->d_status, ctx->d_npos, ctx->d_npk, ctx->d_nlv, ctx->d_ncnt, ctx->d_stile, ctx->d_sst,
              ctx->d_sbits);
@@ -1045,9 +964,7 @@ static int launch_reads(ldg_ctx* ctx, hipStream_t st, int n, const int32_t* M_, 
                ctx->d_recs, ctx->d_lines, ctx->d_scratch, ctx->d_reads);
     LDG_LAUNCH_ON(st, "pilot_field", ldg_k_pilot_field, n, 256, M_, ctx->d_recs, ctx->d_lines, C, ctx->d_scratch);
   }
-  if (!(ctx->skip >> 8 & 1) && ctx->final_hoist) LDG_LAUNCH_ON(st, "final_lines", ldg_k_final_lines_h, g_rows, FINAL_NT, M_, ctx->video, ctx->vread, ctx->vchan, C,
-             ctx->d_recs, ctx->d_lines, ctx->d_blevel, ctx->d_pic, ctx->pic_stride, ctx->d_reads);
-  else if (!(ctx->skip >> 8 & 1)) LDG_LAUNCH_ON(st, "final_lines", ldg_k_final_lines, g_rows, FINAL_NT, M_, ctx->video, ctx->vread, ctx->vchan, C,
+  if (!(ctx->skip >> 8 & 1)) LDG_LAUNCH_ON(st, "final_lines", ldg_k_final_lines, g_rows, FINAL_NT, M_, ctx->video, ctx->vread, ctx->vchan, C,
              ctx->d_recs, ctx->d_lines, ctx->d_blevel, ctx->d_pic, ctx->pic_stride, ctx->d_reads);
   // (pending records become FS_VALID in ldg_k_recs_out, after all groups)
   if (int rc = check_launch(ctx, "tbc kernels")) return rc;
@@ -1114,7 +1031,6 @@ int ldg_decode_reads_async2(ldg_ctx* ctx, int n, const int64_t* read_starts, con
   LDG_TRY(hipSetDevice(ctx->device));
   if (const char* e = getenv("LDG_STAGES")) ctx->stages = atoi(e);   // stage-isolation probes only
   if (const char* e = getenv("LDG_SKIP")) ctx->skip = atoi(e);       // timing probes only: results are garbage
-  if (const char* e = getenv("LDG_DEMOD_SPLIT")) ctx->demod_split = atoi(e) != 0;
   HostProf hp_;
   // consecutive calls' demods alternate between two streams: the next call's demod
   // workgroups take CUs as the current one's last wave drains (its tail, and the
@@ -1250,28 +1166,14 @@ int ldg_decode_reads_async2(ldg_ctx* ctx, int n, const int64_t* read_starts, con
     if (int rc = check_launch(ctx, "ldg_k_probe_pick")) return rc;
     ctx->probes += np;
   }
-  // field-chain groups: consecutive reads, one group per sub-stream.  With
-  // LDG_DEMOD_SPLIT the demod runs group by group (in order on `stream`) and a
-  // group's chain starts when its own reads are demodulated.
+  // field-chain groups: consecutive reads, one group per sub-stream
   const int ng = (ctx->stages & 4) ? std::max(1, std::min(ctx->nsub, n / 4)) : 0;
-  const bool split = ctx->demod_split && ng > 1;
   auto group = [&](int g, int& i0, int& m) {
     i0 = (int)((int64_t)n * g / ng);
     m = (int)((int64_t)n * (g + 1) / ng) - i0;
   };
-  if (ctx->stages & 1) {
-    if (split) {
-      for (int g = 0; g < ng; g++) {
-        int i0, m;
-        group(g, i0, m);
-        if (m > 0)
-          if (int rc = launch_reads(ctx, s, m, dsm + i0, ctx->d_ospill, true, false)) return rc;
-        LDG_TRY(hipEventRecord(call.ev_dg[g], s));
-      }
-    } else if (int rc = launch_reads(ctx, s, n, dsm, ctx->d_ospill, true, false)) {
-      return rc;
-    }
-  }
+  if (ctx->stages & 1)
+    if (int rc = launch_demod(ctx, s, n, dsm)) return rc;
   hp_.mark("demod");
   LDG_TRY(hipEventRecord(call.ev_demod, s));
   call.demod_recorded = true;
@@ -1294,10 +1196,10 @@ int ldg_decode_reads_async2(ldg_ctx* ctx, int n, const int64_t* read_starts, con
     group(g, i0, m);
     if (m <= 0) continue;
     hipStream_t st = ctx->sub[g];
-    LDG_TRY(hipStreamWaitEvent(st, (split && (ctx->stages & 1)) ? call.ev_dg[g] : call.ev_demod, 0));
+    LDG_TRY(hipStreamWaitEvent(st, call.ev_demod, 0));
     if (ctx->frames_recorded) LDG_TRY(hipStreamWaitEvent(st, ctx->ev_frames, 0));
     if (ctx->audio_recorded) LDG_TRY(hipStreamWaitEvent(st, ctx->ev_audio, 0));
-    if (int rc = launch_reads(ctx, st, m, dsm + i0, nullptr, false, true)) return rc;
+    if (int rc = launch_chain(ctx, st, m, dsm + i0)) return rc;
     LDG_TRY(hipEventRecord(call.ev_done[nd++], st));
   hp_.mark("chain");
   }
@@ -1759,7 +1661,7 @@ int ldg_assemble_frames(ldg_ctx* ctx, int n, const int32_t* top_slots, const int
   uint16_t* dst = out;
   if (!(out_is_device && out)) {
     // the context's frame buffers alternate; wait for the last reader of the one written now
-    if (!ctx->fbuf_single) ctx->fb ^= 1;
+    ctx->fb ^= 1;
     if (ctx->fbuf_recorded[ctx->fb]) LDG_TRY(hipStreamWaitEvent(s, ctx->ev_fbuf[ctx->fb], 0));
     dst = ctx->frame_buf(ctx->fb);
   }
@@ -1828,7 +1730,7 @@ int ldg_output_async(ldg_ctx* ctx, int n, const int32_t* top_slots, const int32_
     // the comb on its own stream after this assembly; the output event and the
     // buffer's reader event go behind both the comb's and the .tbc copy
     if (int rc = pal_rgb ? pal_alloc(ctx) : comb_alloc(ctx)) return rc;
-    hipStream_t c = ctx->comb_stream();
+    hipStream_t c = ctx->scomb;
     LDG_TRY(hipEventRecord(ctx->ev_tbc, s));
     LDG_TRY(hipStreamWaitEvent(c, ctx->ev_frames, 0));
     if (pal_rgb) {
@@ -1917,12 +1819,7 @@ static int comb_launch(ldg_ctx* ctx, hipStream_t st, const uint16_t* src, int n,
   if (!d3 && def && !ctx->comb_unfused) {
     // the default 2D comb: split, FilterIQ and output in one row kernel (cv in LDS)
     const int total = n * O.nrows;
-    if (ctx->comb_rows_wg > 0) {
-      const int g = ctx->comb_rows_wg < total ? ctx->comb_rows_wg : total;
-      LDG_LAUNCH_ON(st, "comb_rows", ldg_k_comb_rows, g, 256, src, ctx->comb_abl, dst, ctx->comb_iqw, total);
-    } else {
-      LDG_LAUNCH_ON(st, "comb_fused", ldg_k_comb_fused, total, 256, src, ctx->comb_abl, dst, ctx->comb_iqw);
-    }
+    LDG_LAUNCH_ON(st, "comb_fused", ldg_k_comb_fused, total, 256, src, ctx->comb_abl, dst, ctx->comb_iqw);
     return check_launch(ctx, "comb kernels");
   }
   if (!d3 && def)
@@ -2104,7 +2001,7 @@ int ldg_comb_async(ldg_ctx* ctx, int n) {
   if (ctx->C.system == 0) return ldg_comb_ntsc_async(ctx, n);
   LDG_TRY(hipSetDevice(ctx->device));
   if (int rc = pal_alloc(ctx)) return rc;
-  hipStream_t c = ctx->comb_stream();
+  hipStream_t c = ctx->scomb;
   const int b = ctx->fb;
   LDG_TRY(hipStreamWaitEvent(c, ctx->ev_frames, 0));
   if (int rc = pal_launch(ctx, c, ctx->frame_buf(b), n)) return rc;
@@ -2122,7 +2019,7 @@ int ldg_comb_ntsc_async(ldg_ctx* ctx, int n) {
   if (int rc = comb_alloc(ctx)) return rc;
   // the comb of the frames just assembled, on its own stream (after that assembly);
   // the assembly after next, which rewrites this buffer, waits for ev_fbuf
-  hipStream_t c = ctx->comb_stream();
+  hipStream_t c = ctx->scomb;
   const int b = ctx->fb;
   LDG_TRY(hipStreamWaitEvent(c, ctx->ev_frames, 0));
   if (int rc = comb_launch(ctx, c, ctx->frame_buf(b), n, ctx->comb_rgb)) return rc;

@@ -125,7 +125,7 @@ constexpr int FR = 252, FC = 840, FY0 = 23, FX0 = 70;
 // Per-kernel phase stamps (profiling builds only, -DLDG_STAMPS; tools/kstamps.py):
 // thread 0 of the first KST_BLOCKS workgroups of kernel K records the shader
 // clock at phase boundary i (after a workgroup barrier).
-// K: 0 comb_rows, 1 final_lines, 2 burst_field, 3 sync, 4 burst_lines, 5 philips.
+// K: 0 comb_fused, 1 final_lines, 2 burst_field, 3 sync, 4 burst_lines, 5 philips.
 #ifdef LDG_STAMPS
 constexpr int KST_KERNELS = 6, KST_BLOCKS = 4096, KST_PHASES = 16;
 __device__ unsigned long long g_kst[KST_KERNELS][KST_BLOCKS][KST_PHASES];

@@ -550,10 +550,7 @@ __device__ __forceinline__ uint16_t tbc_pixel(double v, double wow, const SysCon
 #define LDG_FINAL_WAVES 6
 #endif
 // (6 waves per SIMD: 78 VGPRs, six line workgroups per CU, 138 KiB of LDS)
-// HOIST: the evaluation's two knot samples per output are loaded together with the
-// solve's samples (one memory round trip per line instead of two, for more VGPRs)
-template <bool HOIST>
-__device__ __forceinline__ void final_lines_impl(
+__device__ __forceinline__ void final_lines_body(
     const int32_t* __restrict__ smap, const double* __restrict__ video, int64_t vread_stride, int64_t vchan_stride,
     SysConst C, FieldRec* __restrict__ recs, const double* __restrict__ lines, const float* __restrict__ blevel,
     uint16_t* __restrict__ pic, int64_t pic_stride, const ReadDesc* __restrict__ reads) {
@@ -650,14 +647,6 @@ __device__ __forceinline__ void final_lines_impl(
     return (int)(j < 0 ? 0 : (j > n - 1 ? n - 1 : j));
   };
   double yk[NO], yk1[NO];
-  if constexpr (HOIST) {
-#pragma unroll
-    for (int e = 0; e < NO; e++) {
-      const int o = tid + FINAL_NT * e, k = knot(e);
-      yk[e] = (o < W) ? y[k] : 0.0;
-      yk1[e] = (o < W) ? y[k + 1] : 0.0;
-    }
-  }
   __syncthreads();
   KSTAMP(1, 1);
   const double M1 = S.m1, Mn1 = S.mn1;
@@ -739,10 +728,8 @@ __device__ __forceinline__ void final_lines_impl(
     const int k = knot(e);
     kk[e] = k;
     xs[e] = x;
-    if constexpr (!HOIST) {
-      yk[e] = (o < W) ? y[k] : 0.0;
-      yk1[e] = (o < W) ? y[k + 1] : 0.0;
-    }
+    yk[e] = (o < W) ? y[k] : 0.0;
+    yk1[e] = (o < W) ? y[k + 1] : 0.0;
   }
 #pragma unroll
   for (int e = 0; e < NO; e++) {
@@ -767,17 +754,13 @@ __device__ __forceinline__ void final_lines_impl(
   }
 }
 
+// (the body stays an inlined helper: written straight into the kernel, the same source
+// gets another register allocation and nine more instructions)
 extern "C" __global__ __launch_bounds__(FINAL_NT, LDG_FINAL_WAVES) void ldg_k_final_lines(
     const int32_t* __restrict__ smap, const double* __restrict__ video, int64_t vread_stride, int64_t vchan_stride,
     SysConst C, FieldRec* __restrict__ recs, const double* __restrict__ lines, const float* __restrict__ blevel,
     uint16_t* __restrict__ pic, int64_t pic_stride, const ReadDesc* __restrict__ reads) {
-  final_lines_impl<false>(smap, video, vread_stride, vchan_stride, C, recs, lines, blevel, pic, pic_stride, reads);
-}
-extern "C" __global__ __launch_bounds__(FINAL_NT, 5) void ldg_k_final_lines_h(
-    const int32_t* __restrict__ smap, const double* __restrict__ video, int64_t vread_stride, int64_t vchan_stride,
-    SysConst C, FieldRec* __restrict__ recs, const double* __restrict__ lines, const float* __restrict__ blevel,
-    uint16_t* __restrict__ pic, int64_t pic_stride, const ReadDesc* __restrict__ reads) {
-  final_lines_impl<true>(smap, video, vread_stride, vchan_stride, C, recs, lines, blevel, pic, pic_stride, reads);
+  final_lines_body(smap, video, vread_stride, vchan_stride, C, recs, lines, blevel, pic, pic_stride, reads);
 }
 
 // Mark reads still pending after the whole chain as valid.

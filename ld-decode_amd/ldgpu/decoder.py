@@ -247,20 +247,6 @@ class GPUDecoder:
         self.period, self.period_samples = P, D          # exact at 40 MSPS: 3 NTSC / 1 PAL frames
         self.field_nom = int(round(self.rf.freq_hz / self.sysp.fps / 2))
         self.trace = None          # diagnostics: planner steps (tools/miss_probe.py)
-        self.boot_wide = os.environ.get('LDG_BOOT_WIDE', '1') == '1'   # +6.5% on the 60 s bench (tools/bootwide_ab.sh)
-        self.miss_drain = os.environ.get('LDG_MISS_DRAIN', '1') == '1'
-        # LDG_BOOT_AHEAD=1: _hint_ahead in the boot plans, one narrow boot launch fewer.  The
-        # boot reads locate the next fields exactly, but they start mid-field and carry no
-        # VBI, so the first wide launches are planned at the initial MTF: right on a CLV
-        # disc (PAL config 3: +6%), wrong on a CAV one, whose MTF follows the frame number
-        # (NTSC config 2: four wide launches redone per decode, -10%;
-        # profiles/r05_zb_boot_ahead_ab.txt).  Off by default: the capture's disc type is
-        # not known at boot, and the loss on CAV outweighs the gain on CLV.
-        self.boot_ahead = os.environ.get('LDG_BOOT_AHEAD', '0') == '1'
-        # while a drain waits for the launch that holds the missed read, keep `depth`
-        # launches in flight, planned on from the miss (the GPU otherwise idles once
-        # the launches ahead of that one land)
-        self.drain_refill = os.environ.get('LDG_DRAIN_REFILL', '0') == '1'
         # read-start probes (ldg_decode_reads_async2 READ_PROBE): reads whose start the
         # plan predicted are moved on the GPU to the sync peak a one-block probe finds
         # there, so a start that jitters by a sample or two still decodes at the exact
@@ -273,12 +259,10 @@ class GPUDecoder:
         # (profiles/r05_o_probe_ab.txt)
         self.probe_mode = os.environ.get('LDG_PROBE', '1' if self.sysp.name == 'PAL' else 'auto')
         self.probe = self.probe_mode == '1'
-        self.plan_idle_skip = os.environ.get('LDG_PLAN_IDLE', '1') == '1'   # (see _decode_loop)
         self.probe_win = int(0.3 * self.rf.linelen) if hasattr(self.rf, 'linelen') else 760
         self._probe_starts = []            # sorted (start, mtf) of probed reads in flight
         self.plan_guessed = set()
-        self.grid_votes = int(os.environ.get('LDG_GRID_VOTES', '1'))   # _grid_next (1: the previous period's start)
-        self.hist_len = max(16, self.grid_votes * P + 2)                  # valid field starts the planner keeps
+        self.hist_len = 16                 # valid field starts the planner keeps
         # Video cut (ldg_set_video_cut): a steady-state read starts ~10 peaks before its
         # field's vsync (lddecode_core.py:926, the previous field's nextfieldoffset), so its
         # field ends ~276 NTSC / ~326 PAL lines into the read; the demod skips the video,
@@ -302,14 +286,6 @@ class GPUDecoder:
         self.transitions = []              # audio-offset chain: linecount of each transition's field
         self.archive, self.arch_next, self.shard_frames = False, 0, []
         self._out_pending = None           # (frames, pics, audio fields, sink) awaiting their audio
-        # A flushed batch whose audio launch and the previous batch's collection (the
-        # host's one blocking wait besides the records) are deferred until the next
-        # decode launch is issued (_finish_flush): otherwise that wait, which ends only
-        # when the running demod leaves CUs to the audio kernels, sits between the
-        # replay and the next launch, and the demod queue runs dry for ~1 ms per batch.
-        self.defer_flush = os.environ.get('LDG_DEFER_FLUSH', '0') == '1'   # level on NTSC, PAL -8% in one pair (r04_zc): off
-        self._staged = None
-        self._staged_slots = set()         # slots the staged batch still reads (never evicted)
         self.frame_log = None              # callback(lines): the reference's stdout lines of each frame
         self._obufs = None                 # pinned host rings for the asynchronous output path
         self._oring = 0
@@ -421,23 +397,6 @@ class GPUDecoder:
         nx, inf = self.hints[best]
         return (best, nx, inf.status, inf.istop, inf.vbi_framenr, inf.nvsync, [tuple(inf.vsync[q]) for q in range(min(inf.nvsync, 3))])
 
-    def _hint_ahead(self, start):
-        """The next field start seen by a decoded read that starts inside the field starting
-        at `start` (after it by less than half a field; valid or short) and lands about one
-        field after it: a read anywhere before a field's vsync finds the same next field
-        (the boot launch's nominal-spacing guesses, tools/boot_probe.py: reads at 799,232 /
-        1,600,353 / 2,399,232 of the PAL bench capture report the chain's 1,311,073 /
-        2,109,793 / 2,911,072).  None if there is none."""
-        import bisect
-        ks, f = self._hint_keys, self.field_nom
-        i = bisect.bisect_right(ks, start + 4096)
-        while i < len(ks) and ks[i] < start + f // 2:
-            nx, inf = self.hints[ks[i]]
-            if inf.status in (native.FS_VALID, native.FS_SHORT) and 0.95 * f < nx - start < 1.05 * f:
-                return nx
-            i += 1
-        return None
-
     def _hint(self, start):
         """(next start, field info) of the decoded read nearest `start` within 4096 samples, or None.
 
@@ -521,17 +480,6 @@ class GPUDecoder:
                         istop = bool(hinfo.istop)
                         fnr = hinfo.vbi_framenr if hinfo.vbi_framenr != native.VBI_NONE else None
                         clv = bool(hinfo.vbi_isclv)
-                    elif (not guessing and self.boot_ahead and len(hist) < self.period + 2
-                          and (ha := self._hint_ahead(key[0])) is not None):
-                        # boot: a decoded read later in this field (one of the boot launch's
-                        # guesses at the nominal field spacing) already saw where the next
-                        # field starts
-                        located += 1
-                        nxt = ha
-                        valid = True
-                        istop = (not prev_top) if prev_top is not None else self.sysp.topfirst
-                        fnr = (fr + 1) if (fr is not None and not isclv) else None
-                        clv = isclv
                     else:
                         guessing = True
                         if h is not None:
@@ -575,28 +523,13 @@ class GPUDecoder:
         self.plan_complete = frames_left is not None and nframes >= frames_left
         return new, chain
 
-    def _grid_next(self, starts, votes=None):
-        """The next read start on the capture's field grid, r_{k+1} = r_{k+1-mP} + mD, voted
-        over m = 1..votes (the most common value; ties go to the smallest m).  A read start
-        is the absolute position of a sync peak found by argmax on a noisy channel
-        (lddecode_core.py:1204, Field.nextfieldoffset): grid + an independent +-1..2 sample
-        jitter (PAL: r[k+2] - r[k] = 1,600,000 +- 1 about one step in ten).  m = 1 alone
-        carries one jittered start into every P-th prediction after it (half of a 96-read
-        PAL launch wasted, profiles/r04_c_pal_waste_10s.txt); the vote keeps it to that read."""
-        P, D = self.period, self.period_samples
-        votes = votes or self.grid_votes
-        if votes == 1:
-            return starts[-(P - 1)] + D         # the planner's hot path (once per guessed read)
-        counts, best, bestc = {}, None, 0
-        for m in range(1, votes + 1):
-            j = m * P - 1
-            if j > len(starts):
-                break
-            c = starts[-j] + m * D
-            counts[c] = counts.get(c, 0) + 1
-            if counts[c] > bestc:
-                best, bestc = c, counts[c]
-        return best
+    def _grid_next(self, starts):
+        """The next read start on the capture's field grid, r_{k+1} = r_{k+1-P} + D: P fields
+        span D samples exactly.  A read start is the absolute position of a sync peak found
+        by argmax on a noisy channel (lddecode_core.py:1204, Field.nextfieldoffset): grid +
+        an independent +-1..2 sample jitter (PAL: r[k+2] - r[k] = 1,600,000 +- 1 about one
+        step in ten), so one jittered start carries into every P-th prediction after it."""
+        return starts[-(self.period - 1)] + self.period_samples
 
     def _launch(self, keys, protect):
         """Decode `keys` now (launch and wait for everything outstanding)."""
@@ -624,8 +557,7 @@ class GPUDecoder:
             used.update(sl)
         free = [s for s in range(self.capacity) if s not in used]
         if len(free) < len(keys):
-            ss = self._staged_slots
-            for k in [k for k in self.cache if k not in protect and self.cache[k][0] not in ss][:len(keys) - len(free)]:
+            for k in [k for k in self.cache if k not in protect][:len(keys) - len(free)]:
                 free.append(self.cache.pop(k)[0])      # oldest first (insertion / touch order)
             keys = keys[:len(free)]
         if not keys:
@@ -1001,11 +933,9 @@ class GPUDecoder:
                 while self.pending:             # no launch outlives the call (an exception included)
                     self._launch_wait()
                 try:
-                    self._finish_flush()
                     self._emit_pending()
                 finally:
                     self._out_pending = None
-                    self._staged, self._staged_slots = None, set()
                     self.ctx.sync()
                     if self.before_ring_reuse is not None:
                         self.before_ring_reuse()   # the sink's writes from the rings are done
@@ -1037,12 +967,13 @@ class GPUDecoder:
             # through the older one's predicted outcomes, so its demod runs on the GPU
             # while the older one's field kernels finish and the host replays.
             steady = len(hist) >= self.period + 2
-            if self.boot_wide and not steady:
+            if not steady:
                 # once the last plan walked P + 2 fields on decoded reads (cache hits or
                 # hints within 4096 samples), the next fields are located exactly and the
                 # period extrapolation is seeded: go wide before the replay catches up.
                 # (Counting hints alone went wide on the boot launch's nominal-spacing
-                # guesses for PAL, P + 2 = 4, and wasted two whole batches.)
+                # guesses for PAL, P + 2 = 4, and wasted two whole batches.)  +6.5% on the 60 s
+                # bench (profiles/r02_s32_bootwide_ab.txt).
                 steady = self.plan_located >= self.period + 2
             depth = self.depth if steady else 1
             launched = 0
@@ -1056,7 +987,7 @@ class GPUDecoder:
                 # launched wide when this very walk located P + 2 fields on decoded reads, else
                 # cut to the narrow size (a walk's first keys do not depend on how far it goes)
                 narrow = min(self.batch, 8 if self._hint_keys else self.period + 2)
-                probe_wide = not steady and self.boot_wide and bool(self._hint_keys)
+                probe_wide = not steady and bool(self._hint_keys)
                 want = self.batch if (steady or probe_wide) else narrow
                 tp = time.perf_counter()
                 plan, chain = self._plan(nextsample, self.mtf_level, self.last_framenr, self.last_isclv, done == 0,
@@ -1068,12 +999,11 @@ class GPUDecoder:
                         plan = plan[:narrow]
                 self.stats['plan_s'] = self.stats.get('plan_s', 0.0) + time.perf_counter() - tp
                 if not plan:
-                    plan_idle = steady and self.plan_complete and self.plan_idle_skip
+                    plan_idle = steady and self.plan_complete
                     break
                 if not self._launch_async(plan, set(chain)):
                     break
                 launched += 1
-            self._finish_flush()
             frames = []
             eof = False
             missed = None
@@ -1146,17 +1076,9 @@ class GPUDecoder:
             # the replay stopped at a read a newer launch holds: it cannot move before
             # that launch lands, so wait for it rather than plan further ahead (each such
             # plan pins another batch of cached reads; a long capture once filled the cache)
-            while (self.miss_drain and missed is not None and (missed in self.inflight or self._probe_covers(missed))
-                   and self.pending):
+            while missed is not None and (missed in self.inflight or self._probe_covers(missed)) and self.pending:
                 self.stats['drain_waits'] = self.stats.get('drain_waits', 0) + 1
                 self._launch_wait()
-                while (self.drain_refill and steady and (missed in self.inflight or self._probe_covers(missed))
-                       and len(self.pending) < depth):
-                    plan, chain = self._plan(nextsample, self.mtf_level, self.last_framenr, self.last_isclv,
-                                             done == 0, self.batch, hist, frames_left=num_frames - done + 2)
-                    if not plan or not self._launch_async(plan, set(chain)):
-                        break
-                    self.stats['drain_refills'] = self.stats.get('drain_refills', 0) + 1
         return done
 
     def _flush(self, frames, W, H, sink):
@@ -1227,24 +1149,11 @@ class GPUDecoder:
             self.arch_next += len(af)
             af = []
         # the audio runs while the host plans and replays the next batch: this batch's
-        # frames go to the sink at the next flush (or at the end of the decode)
-        self._staged = (frames, pics, af, sink)
-        if self.defer_flush:
-            self._staged_slots = set(tops) | set(bots) | {x.slot for _, x in af}
-        else:
-            self._finish_flush()
-
-    def _finish_flush(self):
-        """Hand the previous batch to the sink (waiting for its audio and output) and
-        launch the staged batch's audio."""
-        if self._staged is None:
-            return
-        staged, self._staged = self._staged, None
+        # frames go to the sink at the next flush (or at the end of the decode), after the
+        # previous batch's (whose audio and output this waits for)
         self._emit_pending()
-        af = staged[2]
         self.ctx.field_audio_async([x.slot for _, x in af], [x.audio_offset for _, x in af])
-        self._staged_slots = set()
-        self._out_pending = staged
+        self._out_pending = (frames, pics, af, sink)
 
     def _emit_pending(self):
         """Collect the outstanding batch's audio and hand its frames to the sink."""

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Interleaved bench runs per environment setting ("-" = none; settings joined by ","):
-#   tools/env_sweep.sh REPS "- LDG_DEPTH=4 LDG_PRIO=1,LDG_DEPTH=4" BENCH-ARGS...
+#   tools/env_sweep.sh REPS "- LDG_DEPTH=4 LDG_PROBE=1,LDG_DEPTH=4" BENCH-ARGS...
 # (the runs' stderr goes to $OUT/env_sweep.err, default bench_outputs/)
 set -e
 REPS=$1; SETS=$2; shift 2
