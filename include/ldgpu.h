@@ -308,6 +308,40 @@ int ldg_set_dropout_opts(ldg_ctx* ctx, const ldg_dropout_opts* opts);
 int ldg_field_dropouts(ldg_ctx* ctx, int n, const int32_t* slots, ldg_dropout* out, int64_t out_stride,
                        int32_t* counts);
 
+/* ---- disc stacking (BUILD-DEFINED: the reference snapshot has none) ----
+ * n_src sources (captures of one side, or copies of the disc) merged into one run of .tbc
+ * frames.  Per output frame and pixel: the candidates are the sources present for the frame
+ * that have no dropout run over the pixel (all present ones where every source has one: a
+ * residual dropout); the output is their median, their rounded mean, or (smart mean) the
+ * rounded mean of the candidates within `threshold` of the median.  NTSC pixels 0 and 1 of
+ * each row (the burst flag pixels) are the lowest-index present source's. */
+#define LDG_STACK_MAX_SOURCES 16
+#define LDG_STACK_MEDIAN 0
+#define LDG_STACK_MEAN 1
+#define LDG_STACK_SMART_MEAN 2
+/* src[s]: host pointer to n_frames packed frames of source s (read only where
+ * present[f * n_src + s] != 0; NULL allowed for a source present nowhere).  runs
+ * [n_frames][n_src][2 parities][320 rows][8][2] (startx, endx) and counts
+ * [n_frames][n_src][2][320], the layout of ldg_k_conceal's entries (frame row y is field
+ * row y >> 1 of parity y & 1); both NULL: no runs anywhere.  A count above 8 is read as 8,
+ * startx < 0 as 0, endx past the row as the row's end.  threshold: uint16 units, 0..65535.
+ * out: host pointer to n_frames packed frames.  n_frames <= max_frames.  LDG_EINVAL (and
+ * ldg_last_error names the argument; the device is not touched) for n_src outside 1..16, an
+ * unknown mode, a threshold out of range, a frame no source is present for, a NULL src[s]
+ * that is present.  The staging buffers are allocated by the first call. */
+int ldg_stack_frames(ldg_ctx* ctx, int n_frames, int n_src, const uint16_t* const* src, const uint8_t* present,
+                     const int16_t* runs, const int32_t* counts, int mode, int threshold, uint16_t* out);
+/* The concealment kernel of frame assembly (ldg_k_conceal) over n host frames in place:
+ * runs [n][2][320][8][2], counts [n][2][320], nrows [n][2] the two fields' line counts
+ * (each -1..320).  Independent of ldg_set_dropout_opts and of the decode's buffers (it
+ * works in the stacker's own). */
+int ldg_conceal_frames(ldg_ctx* ctx, int n, uint16_t* frames, const int16_t* runs, const int32_t* counts,
+                       const int32_t* nrows);
+/* Seconds spent since ldg_create in ldg_stack_frames' host-to-device copies, kernel and
+ * device-to-host copies (the call is synchronous; each phase is timed to its completion),
+ * and its calls: up to n of these four doubles.  Returns the count written. */
+int ldg_stack_stats(ldg_ctx* ctx, double* out, int n);
+
 /* Debug / parity access to the per-read device arrays of a live slot.
  * what: 0..4 demod channels (demod, demod_05, demod_sync, demod_burst, demod_pilot)
  *       [float64, n_out] (demod_05, demod_sync and demod_burst are expanded on request from

@@ -217,6 +217,16 @@ struct ldg_ctx {
   int32_t *d_drop_cnt = nullptr, *d_drop_rows = nullptr, *d_fdrop_cnt = nullptr, *d_fdrop_rows = nullptr;
   int32_t *d_drop_map = nullptr, *d_fdrop_map = nullptr;
   char* h_drop = nullptr;          // pinned: the slots' runs, counts and line counts for the host
+  // Disc stacking (stack.hip), allocated by the first ldg_stack_frames / ldg_conceal_frames:
+  // a stream and buffers of its own, so a decode on this context never sees it.
+  hipStream_t sstack = nullptr;
+  int stack_cap = 0;               // sources the staging holds
+  int64_t stack_src_stride = 0;    // pixels between two sources' frames (a multiple of 8)
+  uint16_t *d_stack_src = nullptr, *d_stack_out = nullptr;
+  int16_t* d_stack_runs = nullptr;
+  int32_t *d_stack_cnt = nullptr, *d_stack_rows = nullptr;
+  uint32_t* d_stack_rowinfo = nullptr;   // [max_frames][625]: StackArgs::rowinfo
+  double stack_t[4] = {};          // ldg_stack_stats: seconds H2D, kernel, D2H; calls
   hipEvent_t ev_fbuf[2] = {nullptr, nullptr};
   bool fbuf_recorded[2] = {false, false};
   hipEvent_t ev_tbc = nullptr;
@@ -421,6 +431,12 @@ int check_launch(ldg_ctx* ctx, const char* what) {
     return LDG_EDEVICE;
   }
   return LDG_OK;
+}
+
+// ldg_k_stack unrolled for N source slots (stack.hip)
+template <int N>
+void stack_launch(ldg_ctx* ctx, hipStream_t s, dim3 grid, const StackArgs& A) {
+  LDG_LAUNCH_ON(s, "stack", ldg_k_stack<N>, grid, STACK_THREADS, A);
 }
 
 // a call's read descriptors (pinned host memory) into their slots; the slot
@@ -664,6 +680,7 @@ int ldg_create(const ldg_config* cfg, ldg_ctx** out) {
 }
 
 static void arch_audio_free(ldg_ctx* ctx);
+static void stack_free(ldg_ctx* ctx);
 
 int ldg_destroy(ldg_ctx* ctx) {
   if (!ctx) return LDG_EINVAL;
@@ -708,6 +725,7 @@ int ldg_destroy(ldg_ctx* ctx) {
                   (void*)ctx->d_fdrop_cnt, (void*)ctx->d_fdrop_rows, (void*)ctx->d_drop_map, (void*)ctx->d_fdrop_map})
     dfree(p);
   if (ctx->h_drop) (void)hipHostFree(ctx->h_drop);
+  stack_free(ctx);
   if (ctx->cap_owned) dfree(ctx->cap);
 
   for (void* p : {(void*)ctx->comb_state, (void*)ctx->comb_abl, (void*)ctx->comb_in, (void*)ctx->comb_rgb,
@@ -1640,6 +1658,205 @@ int ldg_field_dropouts(ldg_ctx* ctx, int n, const int32_t* slots, ldg_dropout* o
     }
     counts[i] = (int32_t)k;
   }
+  return LDG_OK;
+}
+
+// ---- disc stacking (stack.hip; build-defined, DESIGN.md section 7b) ----------------
+static void stack_free(ldg_ctx* ctx) {
+  if (ctx->sstack) {
+    (void)hipStreamSynchronize(ctx->sstack);
+    (void)hipStreamDestroy(ctx->sstack);
+    ctx->sstack = nullptr;
+  }
+  for (void** p : {(void**)&ctx->d_stack_src, (void**)&ctx->d_stack_out, (void**)&ctx->d_stack_runs,
+                   (void**)&ctx->d_stack_cnt, (void**)&ctx->d_stack_rows, (void**)&ctx->d_stack_rowinfo}) {
+    dfree(*p);
+    *p = nullptr;
+  }
+  ctx->stack_cap = 0;
+}
+
+static size_t stack_frame_px(const ldg_ctx* ctx) { return ctx->system == 1 ? (size_t)1135 * 625 : (size_t)910 * 525; }
+
+// staging for n_src sources of max_frames frames, their runs, and the output frames
+static int stack_alloc(ldg_ctx* ctx, int n_src) {
+  if (ctx->stack_cap >= n_src) return LDG_OK;
+  stack_free(ctx);
+  if (hipStreamCreateWithFlags(&ctx->sstack, hipStreamNonBlocking) != hipSuccess) {
+    ctx->sstack = nullptr;
+    ctx->err = "stacking: hipStreamCreate failed";
+    return LDG_EDEVICE;
+  }
+  const size_t F = (size_t)ctx->max_frames, S = (size_t)n_src;
+  ctx->stack_src_stride = (int64_t)((F * stack_frame_px(ctx) + 7) & ~(size_t)7);
+  int rc = 0;
+  rc |= dmalloc(ctx, &ctx->d_stack_src, S * (size_t)ctx->stack_src_stride);
+  rc |= dmalloc(ctx, &ctx->d_stack_out, F * stack_frame_px(ctx));
+  rc |= dmalloc(ctx, &ctx->d_stack_runs, F * S * 2 * STACK_RUNS_STRIDE);
+  rc |= dmalloc(ctx, &ctx->d_stack_cnt, F * S * 2 * MAX_LINES);
+  rc |= dmalloc(ctx, &ctx->d_stack_rows, F * 2);
+  rc |= dmalloc(ctx, &ctx->d_stack_rowinfo, F * 625);
+  if (rc) {
+    stack_free(ctx);
+    ctx->err = "stacking buffers: out of memory";
+    return LDG_ENOMEM;
+  }
+  ctx->stack_cap = n_src;
+  return LDG_OK;
+}
+
+int ldg_stack_frames(ldg_ctx* ctx, int n_frames, int n_src, const uint16_t* const* src, const uint8_t* present,
+                     const int16_t* runs, const int32_t* counts, int mode, int threshold, uint16_t* out) {
+  if (!ctx) return LDG_EINVAL;
+  auto bad = [&](const char* what) {
+    ctx->err = std::string("ldg_stack_frames: ") + what;
+    return LDG_EINVAL;
+  };
+  if (n_src < 1 || n_src > LDG_STACK_MAX_SOURCES) return bad("n_src must be 1..16");
+  if (n_frames < 0 || n_frames > ctx->max_frames) return bad("n_frames must be 0..max_frames");
+  if (mode != LDG_STACK_MEDIAN && mode != LDG_STACK_MEAN && mode != LDG_STACK_SMART_MEAN)
+    return bad("mode must be LDG_STACK_MEDIAN, LDG_STACK_MEAN or LDG_STACK_SMART_MEAN");
+  if (threshold < 0 || threshold > 65535) return bad("threshold must be 0..65535");
+  if (n_frames == 0) return LDG_OK;
+  if (!src || !present || !out) return bad("src, present and out must not be NULL");
+  if ((runs == nullptr) != (counts == nullptr)) return bad("runs and counts must both be given or both be NULL");
+  for (int f = 0; f < n_frames; f++) {
+    bool any = false;
+    for (int s = 0; s < n_src; s++) {
+      if (!present[(size_t)f * n_src + s]) continue;
+      any = true;
+      if (!src[s]) return bad("src[s] is NULL for a source that present marks");
+    }
+    if (!any) return bad("present: a frame has no present source");
+  }
+  LDG_TRY(hipSetDevice(ctx->device));
+  if (int rc = stack_alloc(ctx, n_src)) return rc;
+  hipStream_t st = ctx->sstack;
+  const size_t fpx = stack_frame_px(ctx);
+  auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+  const double t0 = now();
+  // each source's runs of consecutive present frames, packed as in the file
+  for (int s = 0; s < n_src; s++) {
+    for (int f = 0; f < n_frames;) {
+      if (!present[(size_t)f * n_src + s]) {
+        f++;
+        continue;
+      }
+      int e = f + 1;
+      while (e < n_frames && present[(size_t)e * n_src + s]) e++;
+      LDG_TRY(hipMemcpyAsync(ctx->d_stack_src + (size_t)s * ctx->stack_src_stride + (size_t)f * fpx, src[s] + (size_t)f * fpx,
+                             (size_t)(e - f) * fpx * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+      f = e;
+    }
+  }
+  // per frame row: the sources present (bits 0..15) and whether one of them has a run there (bit 31)
+  const int H = ctx->system == 1 ? 625 : 525;
+  std::vector<uint32_t> rowinfo((size_t)n_frames * H);
+  for (int f = 0; f < n_frames; f++) {
+    uint32_t pm = 0;
+    for (int s = 0; s < n_src; s++)
+      if (present[(size_t)f * n_src + s]) pm |= 1u << s;
+    uint32_t* ri = rowinfo.data() + (size_t)f * H;
+    for (int y = 0; y < H; y++) ri[y] = pm;
+    if (!counts) continue;
+    for (int s = 0; s < n_src; s++) {
+      if (!((pm >> s) & 1u)) continue;
+      const int32_t* c = counts + ((size_t)f * n_src + s) * 2 * MAX_LINES;
+      for (int p = 0; p < 2; p++)
+        for (int r = 0; 2 * r + p < H; r++)
+          if (c[p * MAX_LINES + r] > 0) ri[2 * r + p] |= 1u << 31;
+    }
+  }
+  LDG_TRY(hipMemcpyAsync(ctx->d_stack_rowinfo, rowinfo.data(), rowinfo.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  if (runs) {
+    const size_t E = (size_t)n_frames * n_src * 2;
+    LDG_TRY(hipMemcpyAsync(ctx->d_stack_runs, runs, E * STACK_RUNS_STRIDE * sizeof(int16_t), hipMemcpyHostToDevice, st));
+    LDG_TRY(hipMemcpyAsync(ctx->d_stack_cnt, counts, E * MAX_LINES * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  }
+  LDG_TRY(hipStreamSynchronize(st));
+  const double t1 = now();
+  StackArgs A;
+  A.src = ctx->d_stack_src;
+  A.src_stride = ctx->stack_src_stride;
+  A.rowinfo = ctx->d_stack_rowinfo;
+  A.runs = runs ? ctx->d_stack_runs : nullptr;
+  A.counts = runs ? ctx->d_stack_cnt : nullptr;
+  A.out = ctx->d_stack_out;
+  A.n_src = n_src;
+  A.W = ctx->system == 1 ? 1135 : 910;
+  A.H = H;
+  A.ntsc = ctx->system == 0;
+  A.mode = mode;
+  A.threshold = threshold;
+  const dim3 grid((unsigned)A.H, (unsigned)n_frames);
+  // the kernel unrolled for the next size that holds n_src (the slots past n_src are absent)
+  if (n_src <= 1) stack_launch<1>(ctx, st, grid, A);
+  else if (n_src <= 2) stack_launch<2>(ctx, st, grid, A);
+  else if (n_src <= 3) stack_launch<3>(ctx, st, grid, A);
+  else if (n_src <= 4) stack_launch<4>(ctx, st, grid, A);
+  else if (n_src <= 6) stack_launch<6>(ctx, st, grid, A);
+  else if (n_src <= 8) stack_launch<8>(ctx, st, grid, A);
+  else if (n_src <= 12) stack_launch<12>(ctx, st, grid, A);
+  else stack_launch<16>(ctx, st, grid, A);
+  if (int rc = check_launch(ctx, "ldg_k_stack")) return rc;
+  LDG_TRY(hipStreamSynchronize(st));
+  const double t2 = now();
+  LDG_TRY(hipMemcpyAsync(out, ctx->d_stack_out, (size_t)n_frames * fpx * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
+  LDG_TRY(hipStreamSynchronize(st));
+  const double t3 = now();
+  ctx->stack_t[0] += t1 - t0;
+  ctx->stack_t[1] += t2 - t1;
+  ctx->stack_t[2] += t3 - t2;
+  ctx->stack_t[3] += 1;
+  prof_collect(ctx);
+  return LDG_OK;
+}
+
+int ldg_stack_stats(ldg_ctx* ctx, double* out, int n) {
+  if (!ctx || !out || n < 0) return LDG_EINVAL;
+  const int m = n < 4 ? n : 4;
+  for (int i = 0; i < m; i++) out[i] = ctx->stack_t[i];
+  return m;
+}
+
+int ldg_conceal_frames(ldg_ctx* ctx, int n, uint16_t* frames, const int16_t* runs, const int32_t* counts,
+                       const int32_t* nrows) {
+  if (!ctx) return LDG_EINVAL;
+  if (n < 0 || (n && (!frames || !runs || !counts || !nrows))) {
+    ctx->err = "ldg_conceal_frames: n >= 0; frames, runs, counts and nrows must not be NULL";
+    return LDG_EINVAL;
+  }
+  for (int i = 0; i < 2 * n; i++)
+    if (nrows[i] < -1 || nrows[i] > MAX_LINES) {
+      ctx->err = "ldg_conceal_frames: nrows must be -1..320";
+      return LDG_EINVAL;
+    }
+  if (n == 0) return LDG_OK;
+  LDG_TRY(hipSetDevice(ctx->device));
+  if (int rc = stack_alloc(ctx, 1)) return rc;
+  hipStream_t st = ctx->sstack;
+  const size_t fpx = stack_frame_px(ctx);
+  SysConst C{};                    // what ldg_k_conceal reads of it
+  C.system = ctx->system;
+  C.outlinelen = ctx->system == 1 ? 1135 : 910;
+  C.frame_lines = ctx->system == 1 ? 625 : 525;
+  for (int done = 0; done < n;) {
+    const int m = (n - done) < ctx->max_frames ? (n - done) : ctx->max_frames;
+    uint16_t* h = frames + (size_t)done * fpx;
+    LDG_TRY(hipMemcpyAsync(ctx->d_stack_out, h, m * fpx * sizeof(uint16_t), hipMemcpyHostToDevice, st));
+    LDG_TRY(hipMemcpyAsync(ctx->d_stack_runs, runs + (size_t)done * 2 * STACK_RUNS_STRIDE,
+                           (size_t)m * 2 * STACK_RUNS_STRIDE * sizeof(int16_t), hipMemcpyHostToDevice, st));
+    LDG_TRY(hipMemcpyAsync(ctx->d_stack_cnt, counts + (size_t)done * 2 * MAX_LINES, (size_t)m * 2 * MAX_LINES * sizeof(int32_t),
+                           hipMemcpyHostToDevice, st));
+    LDG_TRY(hipMemcpyAsync(ctx->d_stack_rows, nrows + (size_t)done * 2, (size_t)m * 2 * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    LDG_LAUNCH_ON(st, "conceal", ldg_k_conceal, dim3((unsigned)C.frame_lines, (unsigned)m), 64, ctx->d_stack_runs,
+                  ctx->d_stack_cnt, ctx->d_stack_rows, C, ctx->d_stack_out);
+    if (int rc = check_launch(ctx, "ldg_k_conceal")) return rc;
+    LDG_TRY(hipMemcpyAsync(h, ctx->d_stack_out, m * fpx * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
+    LDG_TRY(hipStreamSynchronize(st));
+    done += m;
+  }
+  prof_collect(ctx);
   return LDG_OK;
 }
 

@@ -30,7 +30,12 @@ EXPORTS = ['ldg_create', 'ldg_destroy', 'ldg_last_error', 'ldg_set_filters', 'ld
            'ldg_audio_offsets', 'ldg_comb_async', 'ldg_debug_rf_table',
            'ldg_stream_open', 'ldg_stream_release', 'ldg_stream_seek', 'ldg_stream_window', 'ldg_stream_stats',
            'ldg_stream_close', 'ldg_device_memory',
-           'ldg_dropout_defaults', 'ldg_set_dropout_opts', 'ldg_field_dropouts']
+           'ldg_dropout_defaults', 'ldg_set_dropout_opts', 'ldg_field_dropouts',
+           'ldg_stack_frames', 'ldg_conceal_frames', 'ldg_stack_stats']
+STACK_MAX_SOURCES = 16            # LDG_STACK_MAX_SOURCES
+STACK_MODES = {'median': 0, 'mean': 1, 'smart-mean': 2}      # LDG_STACK_*
+STACK_STATS = ('h2d_s', 'kernel_s', 'd2h_s', 'calls')        # ldg_stack_stats, in order
+FRAME_SHAPE = {'NTSC': (525, 910), 'PAL': (625, 1135)}       # .tbc frame rows, pixels
 MAX_DROPOUTS_PER_LINE = 8         # LDG_MAX_DROPOUTS_PER_LINE
 MAX_LINES = 320                   # rows of the per-slot line arrays (ldg_debug_read)
 STREAM_STATS = ('bytes_read', 'read_s', 'chunks', 'launch_waits', 'launch_wait_s', 'space_wait_s', 'seeks',
@@ -195,6 +200,9 @@ def load(path=None):
     lib.ldg_dropout_defaults.argtypes = [C.c_int, C.POINTER(DropoutOpts)]
     lib.ldg_set_dropout_opts.argtypes = [vp, C.POINTER(DropoutOpts)]
     lib.ldg_field_dropouts.argtypes = [vp, C.c_int, vp, vp, C.c_int64, vp]
+    lib.ldg_stack_frames.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, vp]
+    lib.ldg_conceal_frames.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+    lib.ldg_stack_stats.argtypes = [vp, vp, C.c_int]
     lib.ldg_version.restype = C.c_char_p
     lib.ldg_device_count.restype = C.c_int
     _lib = lib
@@ -612,6 +620,62 @@ class Context:
 
     def comb_reset(self):
         self._check(self.lib.ldg_comb_reset(self.h), 'ldg_comb_reset')
+
+    # ---- disc stacking (build-defined; include/ldgpu.h) ----------
+    def stack_frames(self, sources, present=None, runs=None, counts=None, mode='smart-mean', threshold=3840):
+        """ldg_stack_frames over any number of frames, max_frames a call.  sources: per source
+        an array of n frames (any shape of n * rows * pixels uint16), or None for a source that
+        is present nowhere; present: bool [n, n_src] (None: every source everywhere); runs int16
+        [n, n_src, 2, MAX_LINES, 8, 2] and counts int32 [n, n_src, 2, MAX_LINES] (both None: no
+        runs).  mode: a key of STACK_MODES or its value.  Returns uint16 [n, rows, pixels]."""
+        H, W = FRAME_SHAPE[self.system]
+        n_src = len(sources)
+        srcs = [None if a is None else np.ascontiguousarray(a, dtype=np.uint16).reshape(-1, H * W) for a in sources]
+        ns = {a.shape[0] for a in srcs if a is not None}
+        if len(ns) > 1:
+            raise ValueError('stack_frames: the sources hold different numbers of frames (%s)' % sorted(ns))
+        if present is None:
+            if not ns:
+                raise ValueError('stack_frames: no source given')
+            present = np.ones((ns.pop(), n_src), dtype=np.uint8)
+        pres = np.ascontiguousarray(np.asarray(present) != 0, dtype=np.uint8).reshape(-1, max(n_src, 1))
+        n = pres.shape[0]
+        if (runs is None) != (counts is None):
+            raise ValueError('stack_frames: runs and counts go together')
+        if runs is not None:
+            runs = np.ascontiguousarray(runs, dtype=np.int16).reshape(n, n_src, 2, MAX_LINES, MAX_DROPOUTS_PER_LINE, 2)
+            counts = np.ascontiguousarray(counts, dtype=np.int32).reshape(n, n_src, 2, MAX_LINES)
+        out = np.empty((n, H, W), dtype=np.uint16)
+        step = self.max_frames
+        for f0 in range(0, n, step):
+            m = min(step, n - f0)
+            ptrs = (C.c_void_p * max(n_src, 1))(*[None if a is None else a[f0:].ctypes.data for a in srcs])
+            self._check(self.lib.ldg_stack_frames(
+                self.h, m, n_src, ptrs, pres[f0:].ctypes.data,
+                None if runs is None else runs[f0:].ctypes.data, None if counts is None else counts[f0:].ctypes.data,
+                int(STACK_MODES.get(mode, mode)), int(threshold), out[f0:].ctypes.data), 'ldg_stack_frames')
+        return out
+
+    def conceal_frames(self, frames, runs, counts, nrows):
+        """ldg_conceal_frames: the concealed copy of n frames.  runs int16 [n, 2, MAX_LINES, 8, 2],
+        counts int32 [n, 2, MAX_LINES], nrows int32 [n, 2] (the two fields' line counts)."""
+        H, W = FRAME_SHAPE[self.system]
+        out = np.array(frames, dtype=np.uint16, order='C').reshape(-1, H, W)
+        n = out.shape[0]
+        runs = np.ascontiguousarray(runs, dtype=np.int16).reshape(n, 2, MAX_LINES, MAX_DROPOUTS_PER_LINE, 2)
+        counts = np.ascontiguousarray(counts, dtype=np.int32).reshape(n, 2, MAX_LINES)
+        nrows = np.ascontiguousarray(nrows, dtype=np.int32).reshape(n, 2)
+        self._check(self.lib.ldg_conceal_frames(self.h, n, out.ctypes.data, runs.ctypes.data, counts.ctypes.data,
+                                                nrows.ctypes.data), 'ldg_conceal_frames')
+        return out
+
+    def stack_stats(self):
+        """ldg_stack_stats: seconds in ldg_stack_frames' copies in, kernel and copies out; calls."""
+        out = np.zeros(len(STACK_STATS), dtype=np.float64)
+        n = self.lib.ldg_stack_stats(self.h, out.ctypes.data, out.size)
+        if n < 0:
+            self._check(n, 'ldg_stack_stats')
+        return dict(zip(STACK_STATS[:n], (float(x) for x in out[:n])))
 
     # ---- profiling / tooling -------------------------------------------------------
     def profile(self, on=True):
