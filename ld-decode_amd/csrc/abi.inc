@@ -975,7 +975,8 @@ static int launch_chain(ldg_ctx* ctx, hipStream_t st, int n, const int32_t* M_) 
     for (int pass = 0; pass < 2; pass++) {
       if (!(ctx->skip >> 6 & 1)) LDG_LAUNCH_ON(st, "burst_lines", ldg_k_burst_lines, g_lines, 64, M_, ctx->video, ctx->vread, ctx->vchan, C,
                  ctx->d_recs, ctx->d_lines, ctx->d_blevel, pass, ctx->d_bst, ctx->d_reads);
-      if (!(ctx->skip >> 7 & 1)) LDG_LAUNCH_ON(st, "burst_field", ldg_k_burst_field, n, 64, M_, ctx->d_recs, ctx->d_lines, ctx->d_blevel, C, pass);
+      if (!(ctx->skip >> 7 & 1)) LDG_LAUNCH_ON(st, "burst_field", ldg_k_burst_field, n, 64, M_, ctx->video, ctx->vread, ctx->vchan,
+                 ctx->d_recs, ctx->d_lines, ctx->d_blevel, C, pass, ctx->d_bst);
     }
   } else {
     LDG_LAUNCH_ON(st, "pilot_lines", ldg_k_pilot_lines, g_lines, 64, M_, ctx->video, ctx->vread, ctx->vchan, C,

@@ -287,53 +287,46 @@ __device__ inline int calczc_s(const double* d, int len, int s, double target, i
 }  // namespace
 
 // ---------------------------------------------------------------------------
-// Burst pass, per (read, line): resample demod_burst over [li[l], li[l+1]] to
-// 4fsc pixels 20..59 (lineoffset 0, wow-scaled), then the per-line part of
-// refine_linelocs_burst (lddecode_core.py:1069-1110).
-// grid: (lines per read, n_reads) workgroups of 64 threads, one line each.
-extern "C" __global__ __launch_bounds__(64) void ldg_k_burst_lines(
-    const int32_t* __restrict__ smap, const double* __restrict__ video, int64_t vread_stride, int64_t vchan_stride, SysConst C,
-    FieldRec* __restrict__ recs, double* __restrict__ lines, float* __restrict__ blevel, int pass,
-    const double4* __restrict__ bst, const ReadDesc* __restrict__ reads) {
-  prio_latency();
+// Burst pass, one line: resample demod_burst over [b0, b1] to 4fsc pixels 20..59
+// (lineoffset 0, wow-scaled), then the per-line part of refine_linelocs_burst
+// (lddecode_core.py:1069-1110) into lvl / pv0 / pv1 [l].  One wave.  Returns
+// (uniform) 0, -1 where the reference raises, or -2 (LONG = false only): the 40
+// outputs' window does not fit S, nothing written.  LONG = true takes the
+// outputs in chunks whose windows fit, for a line of any length: line locations
+// extrapolated across a run of bad lines can lie many lines apart, and the
+// reference's scale() does not mind.
+namespace {
 
-  // window rows for 40 outputs: <= 40 * SPL_MAXN / W + 2 * KTR + 4 < 384
-  __shared__ SplineLDS<64, 384> S;
-  __shared__ double s_ba[40], s_t[40], s_g[2][40];
-  const int lane = threadIdx.x;
-  const int slot = smap[blockIdx.y];
-  const int l = blockIdx.x;
-  FieldRec* R = recs + slot;
-  double* LN = lines + (int64_t)slot * LINES_STRIDE;
-  const double* li = LN + (pass == 0 ? LL2 : LL3) * MAX_LINES;
-  // the record and the line's two locations in one memory round trip (clamped indices)
-  const int status = R->status, nl = R->nlines, lc = R->linecount;
-  const double b0 = li[l], b1 = li[l + 1 < MAX_LINES ? l + 1 : MAX_LINES - 1];
-  asm volatile("" ::"v"(b0), "v"(b1), "v"(status), "v"(nl), "v"(lc));
-  if (status != FS_PENDING) return;
-  double* pv0 = LN + PAVG0 * MAX_LINES;
-  double* pv1 = LN + PAVG1 * MAX_LINES;
-  float* lvl = blevel + (int64_t)slot * MAX_LINES;
-  if (l >= nl) return;
-  if (l >= lc) {
-    if (lane == 0) { pv0[l] = 0.0; pv1[l] = 0.0; lvl[l] = 0.0f; }
-    return;
-  }
-  if (py_int(b1) + 1 >= reads[slot].vcut) {   // the window reaches past the read's video cut
-    if (lane == 0) R->status = FS_VCUT;
-    return;
-  }
+using BurstLDS = SplineLDS<64, 384>;   // window rows for 40 outputs: <= 40 * SPL_MAXN / W + 2 * KTR + 4 < 384
+
+template <bool LONG>
+__device__ __forceinline__ int burst_line(const double* __restrict__ video, int64_t vread_stride, int64_t vchan_stride,
+                                          const SysConst& C, int64_t len, const double4* __restrict__ bst, int slot, int l,
+                                          double b0, double b1, int lane, BurstLDS& S, double* s_ba, double* s_t,
+                                          double (*s_g)[40], float* lvl, double* pv0, double* pv1) {
   // demod_burst from the demod channel and the demod's per-chunk states (chan.hpp)
   const BurstSrc bur(bst, video + (int64_t)slot * vread_stride + (int64_t)CH_DEMOD * vchan_stride, slot, C);
   const double wow = (b1 - b0) / (double)C.linelen;
   const int W = C.outlinelen;
-  const int rc = spline_block<64, 4>(bur, R->n_out, b0, b1, W, 20, 60, lane, S,
-                                  [&](int o, double v) { s_ba[o - 20] = v * wow; });
-  if (rc < 0) {
-    if (lane == 0) R->status = FS_TBC;   // benign race: every writer stores the same value
-    return;
+  if constexpr (!LONG) {
+    const int rc = spline_block<64, 4>(bur, len, b0, b1, W, 20, 60, lane, S,
+                                    [&](int o, double v) { s_ba[o - 20] = v * wow; });
+    if (rc < 0) return rc;
+    __syncthreads();
+  } else {
+    // oc outputs span < oc * n / W + 2 rows, their window 2 KTR + 4 more (one output: its
+    // window alone, whatever the line's length)
+    const int64_t n64 = py_int(b1) - py_int(b0);
+    const int64_t oc64 = n64 > 0 ? ((int64_t)(BurstLDS::cap - 2 * KTR - 16) * W) / n64 : 40;
+    const int oc = oc64 < 1 ? 1 : (oc64 > 40 ? 40 : (int)oc64);
+    for (int o0 = 20; o0 < 60; o0 += oc) {
+      const int o1 = o0 + oc < 60 ? o0 + oc : 60;
+      const int rc = spline_block<64>(bur, len, b0, b1, W, o0, o1, lane, S,
+                                      [&](int o, double v) { s_ba[o - 20] = v * wow; });
+      if (rc < 0) return -1;
+      __syncthreads();
+    }
   }
-  __syncthreads();
   // the burst statistics on the whole wave (numpy's pairwise sums via wave_pw_block)
   double* ba = s_ba;
   double* tt = s_t;
@@ -383,7 +376,7 @@ extern "C" __global__ __launch_bounds__(64) void ldg_k_burst_lines(
   if ((VT >> lane) & 1) s_g[1][__popcll(VT & below)] = off;
   if ((VF >> lane) & 1) s_g[0][__popcll(VF & below)] = off;
   __syncthreads();
-  if (lane != 0) return;
+  if (lane != 0) return 0;
   double p0 = 0.0, p1 = 0.0;
   float out_level = lf;
   if (((lv / hzs) > 30) || (sd / hzs) < 3) {
@@ -398,18 +391,64 @@ extern "C" __global__ __launch_bounds__(64) void ldg_k_burst_lines(
   lvl[l] = out_level;
   pv0[l] = p0;
   pv1[l] = p1;
+  return 0;
+}
+
+constexpr float BURST_LINE_LONG = -1.0f;   // lvl[l] of a line left to ldg_k_burst_field (levels are >= 0 here)
+
+}  // namespace
+
+// grid: (lines per read, n_reads) workgroups of 64 threads, one line each.
+extern "C" __global__ __launch_bounds__(64) void ldg_k_burst_lines(
+    const int32_t* __restrict__ smap, const double* __restrict__ video, int64_t vread_stride, int64_t vchan_stride, SysConst C,
+    FieldRec* __restrict__ recs, double* __restrict__ lines, float* __restrict__ blevel, int pass,
+    const double4* __restrict__ bst, const ReadDesc* __restrict__ reads) {
+  prio_latency();
+
+  __shared__ BurstLDS S;
+  __shared__ double s_ba[40], s_t[40], s_g[2][40];
+  const int lane = threadIdx.x;
+  const int slot = smap[blockIdx.y];
+  const int l = blockIdx.x;
+  FieldRec* R = recs + slot;
+  double* LN = lines + (int64_t)slot * LINES_STRIDE;
+  const double* li = LN + (pass == 0 ? LL2 : LL3) * MAX_LINES;
+  // the record and the line's two locations in one memory round trip (clamped indices)
+  const int status = R->status, nl = R->nlines, lc = R->linecount;
+  const double b0 = li[l], b1 = li[l + 1 < MAX_LINES ? l + 1 : MAX_LINES - 1];
+  asm volatile("" ::"v"(b0), "v"(b1), "v"(status), "v"(nl), "v"(lc));
+  if (status != FS_PENDING) return;
+  double* pv0 = LN + PAVG0 * MAX_LINES;
+  double* pv1 = LN + PAVG1 * MAX_LINES;
+  float* lvl = blevel + (int64_t)slot * MAX_LINES;
+  if (l >= nl) return;
+  if (l >= lc) {
+    if (lane == 0) { pv0[l] = 0.0; pv1[l] = 0.0; lvl[l] = 0.0f; }
+    return;
+  }
+  if (py_int(b1) + 1 >= reads[slot].vcut) {   // the window reaches past the read's video cut
+    if (lane == 0) R->status = FS_VCUT;
+    return;
+  }
+  const int rc = burst_line<false>(video, vread_stride, vchan_stride, C, R->n_out, bst, slot, l, b0, b1, lane, S, s_ba, s_t,
+                                   s_g, lvl, pv0, pv1);
+  if (rc < 0 && lane == 0) {
+    if (rc == -2) lvl[l] = BURST_LINE_LONG;   // a line several times its nominal length: ldg_k_burst_field's
+    else R->status = FS_TBC;                  // benign race: every writer stores the same value
+  }
 #ifdef LDG_STAMPS
-  if (blockIdx.x < KST_BLOCKS) g_kst[4][blockIdx.x][7] = __builtin_readcyclecounter();
+  if (lane == 0 && rc == 0 && blockIdx.x < KST_BLOCKS) g_kst[4][blockIdx.x][7] = __builtin_readcyclecounter();
 #endif
 }
 
 // Per-read part of refine_linelocs_burst (lddecode_core.py:1112-1133) and, on
-// the second pass, apply_offsets (:1161-1162, 1184-1186).  grid: n_reads x 64.
-extern "C" __global__ __launch_bounds__(64) void ldg_k_burst_field(const int32_t* __restrict__ smap,
-                                                                   FieldRec* __restrict__ recs,
-                                                                   double* __restrict__ lines,
-                                                                   float* __restrict__ blevel, SysConst C,
-                                                                   int pass) {
+// the second pass, apply_offsets (:1161-1162, 1184-1186); before it, the lines
+// ldg_k_burst_lines left over (BURST_LINE_LONG), one after another.
+// grid: n_reads x 64.
+extern "C" __global__ __launch_bounds__(64) void ldg_k_burst_field(
+    const int32_t* __restrict__ smap, const double* __restrict__ video, int64_t vread_stride, int64_t vchan_stride,
+    FieldRec* __restrict__ recs, double* __restrict__ lines, float* __restrict__ blevel, SysConst C, int pass,
+    const double4* __restrict__ bst) {
   prio_latency();
 
   __shared__ double s_c0[512], s_c1[512];
@@ -425,9 +464,29 @@ extern "C" __global__ __launch_bounds__(64) void ldg_k_burst_field(const int32_t
   double* LN = lines + (int64_t)slot * LINES_STRIDE;
   const double* li = LN + (pass == 0 ? LL2 : LL3) * MAX_LINES;
   double* lo = LN + (pass == 0 ? LL3 : LL4) * MAX_LINES;
-  const double* pv0 = LN + PAVG0 * MAX_LINES;
-  const double* pv1 = LN + PAVG1 * MAX_LINES;
+  double* pv0 = LN + PAVG0 * MAX_LINES;
+  double* pv1 = LN + PAVG1 * MAX_LINES;
   float* lvl = blevel + (int64_t)slot * MAX_LINES;
+  {
+    bool any_long = false;
+    for (int l0 = 0; l0 < nl; l0 += 64) any_long |= (l0 + lane < nl) && lvl[l0 + lane] == BURST_LINE_LONG;
+    if (__any(any_long)) {
+      __shared__ BurstLDS S;
+      __shared__ double s_ba[40], s_t[40], s_gr[2][40];
+      const int lc = R->linecount;
+      const int64_t len = R->n_out;
+      for (int l = 0; l < lc; l++) {
+        if (lvl[l] != BURST_LINE_LONG) continue;
+        const int rc = burst_line<true>(video, vread_stride, vchan_stride, C, len, bst, slot, l, li[l], li[l + 1], lane, S,
+                                        s_ba, s_t, s_gr, lvl, pv0, pv1);
+        __syncthreads();
+        if (rc < 0) {
+          if (lane == 0) R->status = FS_TBC;
+          return;
+        }
+      }
+    }
+  }
   KSTAMP(2, 0);
   // phaseaverages_cut: rows with a nonzero entry (NaN counts as nonzero), in
   // order -- a ballot compaction -- then np.median of each column (wave bitonic sort)
