@@ -71,9 +71,10 @@ extern "C" {
                            * store and its reload (another demod workgroup ran on the CU
                            * while this one was switched out: compute-wave save/restore
                            * on a shared GPU): its result is void, decode the read again */
-#define LDG_FS_VCUT 9     /* a field kernel needed the video channel past the read's video
-                           * cut (ldg_set_video_cut): its result is void, decode the read
-                           * again in full (ldg_decode_reads_async2, full[i] = 1)          */
+#define LDG_FS_VCUT 9     /* a field kernel needed a channel past the read's video cut, or
+                           * the field's audio lies where the cut trimmed it
+                           * (ldg_set_video_cut, ldg_tail_plan): its result is void, decode
+                           * the read again in full (ldg_decode_reads_async2, full[i] = 1)  */
 
 #define LDG_VBI_NONE (-2147483647 - 1) /* Python None in Field.vbi */
 
@@ -232,6 +233,23 @@ int ldg_decode_reads_async2(ldg_ctx* ctx, int n, const int64_t* read_starts, con
  * full[i] = 1.  With a cut past the field (NTSC: ~10 lines before its vsync + 266
  * lines), a read skips its tail blocks' video IFFT and stores. */
 int ldg_set_video_cut(ldg_ctx* ctx, int64_t out_samples);
+
+/* What a read's video cut trims besides the video channels (host code, no context, no
+ * device; for tests of the geometry).  A read of n_out outputs, n_audio 2.5 MHz and
+ * n_audio2 625 kHz audio samples under the cut vcut (0: none):
+ *   out[0]  first 2.5 MHz sample that no live block of audio phase 2 reads   (-1: no cut)
+ *   out[1]  first 625 kHz output that is not produced                        (-1: no cut)
+ *   out[2]  audio phase-2 blocks computed      out[3]  demod blocks that make audio slices
+ *   out[4]  demod blocks that store demod_05
+ * The audio is trimmed only when ceil(vcut / 64) <= out[1], i.e. when the last block of
+ * audio phase 2 serves nothing below the cut (NTSC's default cut: yes; PAL's: no).  A
+ * field whose 48 kHz audio or line refinement would reach trimmed data comes back
+ * LDG_FS_VCUT like one whose video does. */
+int ldg_tail_plan(int64_t n_out, int64_t n_audio, int64_t n_audio2, int64_t vcut, int64_t out[5]);
+/* The span of input-sample positions ldg_field_audio can form from a field's nlines final
+ * line locations (out[0] lowest, out[1] highest; sample int(position / 64) of the 625 kHz
+ * audio is read): what the device's guard holds against out[1] of ldg_tail_plan.  Host code. */
+int ldg_audio_reach(const double* lines, int nlines, int linecount, double linelen, double out[2]);
 int ldg_decode_reads_wait(ldg_ctx* ctx, ldg_field_info* info);
 
 /* 48 kHz audio for fields in the given slots with the given starting time

@@ -966,7 +966,7 @@ static int launch_chain(ldg_ctx* ctx, hipStream_t st, int n, const int32_t* M_) 
   // workgroups per read, each holding its LDS while it found its row out of range)
   const dim3 g_lines((unsigned)(C.frame_lines / 2 + 5), (unsigned)n), g_rows((unsigned)(C.frame_lines / 2 + 1), (unsigned)n);
   if (!(ctx->skip >> 3 & 1)) LDG_LAUNCH_ON(st, "hsync_lines", ldg_k_hsync_lines, g_lines, 64, M_, ctx->video, ctx->vread, ctx->vchan, C,
-             ctx->d_recs, ctx->d_lines, ctx->d_bad);
+             ctx->d_recs, ctx->d_lines, ctx->d_bad, ctx->d_reads);
   if (!(ctx->skip >> 4 & 1)) LDG_LAUNCH_ON(st, "hsync_field", ldg_k_hsync_field, n, 256, M_, C, ctx->d_recs, ctx->d_lines, ctx->d_bad);
   if (!(ctx->skip >> 5 & 1)) LDG_LAUNCH_ON(st, "philips", ldg_k_philips, n, 192, M_, ctx->video, ctx->vread, ctx->vchan, C, ctx->d_recs,
              ctx->d_lines, ctx->d_reads);
@@ -976,12 +976,13 @@ static int launch_chain(ldg_ctx* ctx, hipStream_t st, int n, const int32_t* M_) 
       if (!(ctx->skip >> 6 & 1)) LDG_LAUNCH_ON(st, "burst_lines", ldg_k_burst_lines, g_lines, 64, M_, ctx->video, ctx->vread, ctx->vchan, C,
                  ctx->d_recs, ctx->d_lines, ctx->d_blevel, pass, ctx->d_bst, ctx->d_reads);
       if (!(ctx->skip >> 7 & 1)) LDG_LAUNCH_ON(st, "burst_field", ldg_k_burst_field, n, 64, M_, ctx->video, ctx->vread, ctx->vchan,
-                 ctx->d_recs, ctx->d_lines, ctx->d_blevel, C, pass, ctx->d_bst);
+                 ctx->d_recs, ctx->d_lines, ctx->d_blevel, C, pass, ctx->d_bst, ctx->d_reads);
     }
   } else {
     LDG_LAUNCH_ON(st, "pilot_lines", ldg_k_pilot_lines, g_lines, 64, M_, ctx->video, ctx->vread, ctx->vchan, C,
                ctx->d_recs, ctx->d_lines, ctx->d_scratch, ctx->d_reads);
-    LDG_LAUNCH_ON(st, "pilot_field", ldg_k_pilot_field, n, 256, M_, ctx->d_recs, ctx->d_lines, C, ctx->d_scratch);
+    LDG_LAUNCH_ON(st, "pilot_field", ldg_k_pilot_field, n, 256, M_, ctx->d_recs, ctx->d_lines, C, ctx->d_scratch,
+               ctx->d_reads);
   }
   if (!(ctx->skip >> 8 & 1)) LDG_LAUNCH_ON(st, "final_lines", ldg_k_final_lines, g_rows, FINAL_NT, M_, ctx->video, ctx->vread, ctx->vchan, C,
              ctx->d_recs, ctx->d_lines, ctx->d_blevel, ctx->d_pic, ctx->pic_stride, ctx->d_reads);
@@ -1030,6 +1031,47 @@ static void read_geometry(ReadDesc& r, int64_t start) {
   r.n_blocks = (int32_t)((r.end - r.s0 + BLOCKSTEP - 1) / BLOCKSTEP);
   r.n_audio = (int32_t)((r.end - r.s0) / AUDIO_DIV1 + 1);
   r.n_audio2 = r.n_audio / AUDIO_DIV2;
+  const TailPlan tp = tail_plan(r.n_audio, r.n_audio2, r.vcut);   // r.vcut is set before the geometry
+  r.acut1 = tp.acut1;
+  r.acut2 = tp.acut2;
+}
+
+// The tail plan of a read of this geometry under the video cut vcut (tail.hpp), for tests:
+// out = {acut1, acut2, live audio phase-2 blocks, demod blocks that make audio slices,
+// demod blocks that store demod_05}; -1 for "no cut".  Needs no context and no GPU.
+int ldg_tail_plan(int64_t n_out, int64_t n_audio, int64_t n_audio2, int64_t vcut, int64_t out[5]) {
+  if (!out || n_out < 0 || n_out > MAX_NOUT || n_audio < 0 || n_audio > MAX_NAUDIO || n_audio2 < 0 ||
+      n_audio2 > MAX_NAUDIO2 || vcut < 0)
+    return LDG_EINVAL;
+  const TailPlan tp = tail_plan((int)n_audio, (int)n_audio2, vcut > 0 ? vcut : INT64_MAX);
+  const int n_blocks = (int)((n_out - 1 + BLOCKSTEP - 1) / BLOCKSTEP), n_mid = a2_n_mid((int)n_audio);
+  out[0] = tp.acut1 == ACUT_NONE ? -1 : tp.acut1;
+  out[1] = tp.acut2 == ACUT_NONE ? -1 : tp.acut2;
+  out[2] = out[3] = out[4] = 0;
+  for (int j = 0; j <= n_mid + 1; j++) out[2] += !a2_block_dead(j, n_mid, tp.acut2);
+  for (int b = 0; b < n_blocks; b++) {
+    out[3] += !a1_block_dead(b, tp.acut1);
+    out[4] += !(vcut > 0 && (int64_t)b * BLOCKSTEP >= vcut);
+  }
+  return LDG_OK;
+}
+
+// The span of sample positions ldg_k_audio_ds can form from a field's final line
+// locations (tail.hpp; the device guard flags FS_VCUT unless it lies in [0, 64 acut2)):
+// out = {lowest position, highest position}.  Needs no context and no GPU.
+int ldg_audio_reach(const double* lines, int nlines, int linecount, double linelen, double out[2]) {
+  if (!lines || !out || nlines <= 0 || nlines > MAX_LINES || linecount < 0) return LDG_EINVAL;
+  double lo = __builtin_inf(), hi = -__builtin_inf();
+  for (int il = 0; il <= audio_last_line(nlines, linecount); il++) {
+    double a, b;
+    audio_line_span(lines, nlines, il, linelen, a, b);
+    if (!(a == a)) { lo = hi = a; break; }
+    lo = std::min(lo, a);
+    hi = std::max(hi, b);
+  }
+  out[0] = lo;
+  out[1] = hi;
+  return LDG_OK;
 }
 
 // ldg_k_probe_pick's half-window: it moves a probed read by at most this many samples
@@ -1154,6 +1196,7 @@ int ldg_decode_reads_async2(ldg_ctx* ctx, int n, const int64_t* read_starts, con
       pr.n_audio = (int32_t)((pr.end - pr.s0) / AUDIO_DIV1 + 1);
       pr.n_audio2 = pr.n_audio / AUDIO_DIV2;
       pr.vcut = 0;                                // the demod stops after the sync channel
+      pr.acut1 = pr.acut2 = ACUT_NONE;
       hpr[np] = pr;
       hps[np++] = smap[i];
     }

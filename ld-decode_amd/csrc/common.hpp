@@ -59,10 +59,12 @@ struct ReadDesc {
   int32_t n_audio;        // ((end - s0) // 16) + 1
   int32_t n_audio2;       // n_audio // 4
   int32_t filt_slot;      // index of the RF filter table (RFVideo * MTF**mtf)
-  int32_t pad_;
-  int64_t vcut;           // demod outputs from here on need no video / burst / pilot channel
-                          // (blocks at or past it stop after the sync channel; a field kernel
+  int32_t acut1;          // tail.hpp: first audio-1 sample no live audio phase-2 block reads (ACUT_NONE: no cut)
+  int64_t vcut;           // demod outputs from here on need no video / burst / pilot / demod_05 channel
+                          // (blocks at or past it keep only the sync channel; a field kernel
                           // that reaches past it flags FS_VCUT)
+  int32_t acut2;          // tail.hpp: first audio-2 output that is not produced (ACUT_NONE: no cut)
+  int32_t pad_;
 };
 
 // System/filter scalars (lddecode_core.py:30-117, 119-279)

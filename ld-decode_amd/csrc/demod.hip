@@ -20,6 +20,7 @@
 #include "fft8k.hpp"
 #include "iir.hpp"
 #include "chan.hpp"
+#include "tail.hpp"
 
 using namespace ldg;
 
@@ -453,7 +454,9 @@ __device__ __forceinline__ void demod_body(LDG_DEMOD_PARAMS) {
     Pairs X;
     if (!(kProbe & 64)) split_pairs(X_, twk, tid, X);
     else for (int c = 0; c < 5; c++) { X.a[c] = X_[tid + 1024 * c]; X.b[c] = X.a[c]; }
-    {
+    // (a block whose audio-1 samples all lie past the read's audio cut makes none: only the
+    // dead last block of audio phase 2 would read them, tail.hpp; uniform over the workgroup)
+    if (!(CUT && a1_block_dead(b, rd.acut1))) {
       // audio carrier slices (lddecode_core.py:321-328): thread t < 512 takes
       // bin k = a0 + t into slot j = t; thread t >= 512 the mirrored bin
       // k = a0 + 1 + (t - 512), conjugated, into slot j = a0 + 1024 - k
@@ -592,12 +595,15 @@ __device__ __forceinline__ void demod_body(LDG_DEMOD_PARAMS) {
     // demod_05 is stored at full rate for refine_linelocs_hsync and the PAL pilot
     // windows (rebuilding those windows by the 65-tap FIR in the field kernels
     // instead measured 3.6% slower end to end, profiles/r03_z_d05_ab.txt)
+    // (not past the read's video cut: its readers, refine_linelocs_hsync and the pilot
+    // windows, check, FS_VCUT; uniform over the workgroup)
     double* o = vout + (int64_t)CH_05 * vchan_stride;
+    const bool st05 = !kProbeNoStore && !(CUT && (int64_t)off >= rd.vcut);
 #pragma unroll
     for (int q = 0; q < 8; q++) {
       const int m = t + T * q;
       const double v0 = zr[q].x * inv, v1 = zr[q].y * inv;
-      if (!kProbeNoStore) {
+      if (st05) {
         // block position p lands at rolled position (p - 32) mod 16384 (even: p0 + 1 never wraps);
         // the wave's 64 pairs are all kept or all dropped except at the block ends
         const int p0 = (2 * m - BLOCKCUT_END) & (BLOCKLEN - 1);
@@ -809,6 +815,9 @@ extern "C" __global__ __launch_bounds__(64) void ldg_k_probe_pick(const int32_t*
       r.n_blocks = (int32_t)((r.end - r.s0 + BLOCKSTEP - 1) / BLOCKSTEP);
       r.n_audio = (int32_t)((r.end - r.s0) / AUDIO_DIV1 + 1);
       r.n_audio2 = r.n_audio / AUDIO_DIV2;
+      const TailPlan tp = tail_plan(r.n_audio, r.n_audio2, r.vcut);
+      r.acut1 = tp.acut1;
+      r.acut2 = tp.acut2;
       if (r.n_out <= MAX_NOUT && r.n_blocks <= MAX_BLOCKS_PER_READ) reads[slot] = r;
     }
     status[slot] = 0;
@@ -837,6 +846,9 @@ extern "C" __global__ __launch_bounds__(A1_T) void ldg_k_audio1(
   const int b = blockIdx.x % MAX_BLOCKS_PER_READ;
   const ReadDesc rd = reads[slot];
   if (b >= rd.n_blocks || status[slot] == FS_EOF) return;
+  // past the read's audio cut the demod made no slices, and only the dead last block of
+  // phase 2 would read this block's samples (and the zeroed tail after the last one)
+  if (a1_block_dead(b, rd.acut1)) return;
   const int off = b * BLOCKSTEP;
   const int copylen = (off + (BLOCKLEN - BLOCKCUT) > rd.n_out) ? rd.n_out - off : BLOCKSTEP;
   constexpr double TAU = 6.283185307179586;
@@ -888,8 +900,7 @@ extern "C" __global__ __launch_bounds__(A1_T) void ldg_k_audio1(
 // two middle + last blocks; the static_assert below holds that bound).
 constexpr int AUDIO2_JMAX = 4;
 constexpr int AUDIO2_WG = 2 * AUDIO2_JMAX;
-static_assert((MAX_NAUDIO - 2 * (BLOCKLEN - 64 * AUDIO_DIV2) + (BLOCKLEN - 64 * AUDIO_DIV2) - 1) /
-                          (BLOCKLEN - 64 * AUDIO_DIV2) + 2 <= AUDIO2_JMAX,
+static_assert((MAX_NAUDIO - 2 * A2_JUMP + A2_JUMP - 1) / A2_JUMP + 2 <= AUDIO2_JMAX,
               "audio phase 2: a read needs more blocks than the grid has");
 extern "C" __global__ __launch_bounds__(1024) void ldg_k_audio2(
     const int32_t* __restrict__ smap, const ReadDesc* __restrict__ reads, const double2* __restrict__ tw, const double2* __restrict__ lpf2,
@@ -907,12 +918,12 @@ extern "C" __global__ __launch_bounds__(1024) void ldg_k_audio2(
   if (status[slot] == FS_EOF) return;
   const ReadDesc rd = reads[slot];
   const int n_in = rd.n_audio, n_out = rd.n_audio2;
-  constexpr int SKIP = 64;
-  constexpr int JUMP = BLOCKLEN - SKIP * AUDIO_DIV2;     // 16128
-  const int span = n_in - JUMP - JUMP;
-  const int n_mid = span > 0 ? (span + JUMP - 1) / JUMP : 0;
+  constexpr int SKIP = A2_SKIP;
+  const int n_mid = a2_n_mid(n_in);
   if (j > n_mid + 1) return;
-  const int start = (j == 0) ? 0 : (j <= n_mid ? JUMP * j : n_in - BLOCKLEN - 1);
+  // the last block of a read whose audio is cut: all its outputs are >= acut2 (tail.hpp)
+  if (a2_block_dead(j, n_mid, rd.acut2)) return;
+  const int start = a2_block_start(j, n_mid, n_in);
   const double* src = audio1 + (int64_t)slot * aread_stride + (int64_t)ch * achan_stride + start;
 #pragma unroll
   for (int q = 0; q < 8; q++) {
@@ -947,7 +958,7 @@ extern "C" __global__ __launch_bounds__(1024) void ldg_k_audio2(
   fft_lds<AUDIO2_BLOCK, 512, true>(X_, tw, tid);   // threads >= 512 only join barriers
   double* dst = audio2 + (int64_t)slot * a2read_stride + (int64_t)ch * a2chan_stride;
   const double scale = 1.0 / (double)AUDIO2_BLOCK / (double)AUDIO_DIV2;
-  const int last_start = n_out - (AUDIO2_BLOCK - SKIP);
+  const int last_start = a2_last_start(n_out);
 #pragma unroll
   for (int e = 0; e < 4; e++) {
     const int p = tid + 1024 * e;

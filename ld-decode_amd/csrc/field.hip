@@ -772,7 +772,8 @@ __device__ void hsync_line(const Src& d05, int64_t len, const SysConst& C, int i
 
 extern "C" __global__ __launch_bounds__(64) void ldg_k_hsync_lines(
     const int32_t* __restrict__ smap, const double* __restrict__ video, int64_t vread_stride, int64_t vchan_stride,
-    SysConst C, FieldRec* __restrict__ recs, double* __restrict__ lines, int8_t* __restrict__ bad) {
+    SysConst C, FieldRec* __restrict__ recs, double* __restrict__ lines, int8_t* __restrict__ bad,
+    const ReadDesc* __restrict__ reads) {
   prio_latency();
 
   __shared__ double s_tmp[20];
@@ -794,6 +795,20 @@ extern "C" __global__ __launch_bounds__(64) void ldg_k_hsync_lines(
   // demod_05 as the demod stored it
   const double* d05 = video + (int64_t)slot * vread_stride + (int64_t)CH_05 * vchan_stride;
   const bool lb = lbi != 0;
+  {
+    // Past the read's video cut demod_05 is not stored.  hsync_line reads, from its
+    // start s = v (v - 200 on lines 0..8): the crossing search [int(s), int(s) + 400],
+    // so zc <= s + 400; the window int(s - 2 fr) .. int(s + 2 fr); and the windows
+    // int(zc - fr) .. int(zc + 3 fr) <= s + 400 + 3 fr.  A negative index or slice
+    // start wraps to the read's end (Python indexing), which needs s - 2 fr >= 0 and
+    // zc - fr >= s - 1 - fr >= 0.  One bound for all, with two samples to spare:
+    const int64_t vcut = reads[slot].vcut;
+    const double s = i < 9 ? v - 200 : v, fr = C.freq;
+    if (vcut != INT64_MAX && !(s - 2 * fr - 2 >= 0 && s + 400 + 3 * fr + 2 < (double)vcut)) {
+      if (lane == 0) R->status = FS_VCUT;
+      return;
+    }
+  }
   double out;
   int flag;
   hsync_line(d05, len, C, i, v, lb, lane, s_tmp, out, flag);

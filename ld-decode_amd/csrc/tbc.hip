@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include "common.hpp"
 #include "field_rec.hpp"
+#include "tail.hpp"
 #include "pyops.hpp"
 #include "chan.hpp"
 
@@ -394,6 +395,24 @@ __device__ __forceinline__ int burst_line(const double* __restrict__ video, int6
   return 0;
 }
 
+// The audio guard (tail.hpp), on a read's final line locations in LDS: does
+// ldg_k_audio_ds reach an audio-2 sample the read's audio cut left unmade?  It runs
+// after the replay has accepted the read (for the sharded archive much later), so the
+// read is flagged FS_VCUT here, and decoded again in full, before that.
+__device__ __forceinline__ bool audio_reach_bad(const double* s_lf, int nl, int lc, const SysConst& C, int32_t acut2,
+                                                int tid, int nt) {
+  bool bad = false;
+  if (acut2 != ACUT_NONE) {
+    const int last = audio_last_line(nl, lc);
+    for (int il = tid; il <= last; il += nt) {
+      double a, b;
+      audio_line_span(s_lf, nl, il, (double)C.linelen, a, b);
+      bad |= !audio_span_ok(a, b, acut2);
+    }
+  }
+  return bad;
+}
+
 constexpr float BURST_LINE_LONG = -1.0f;   // lvl[l] of a line left to ldg_k_burst_field (levels are >= 0 here)
 
 }  // namespace
@@ -448,7 +467,7 @@ extern "C" __global__ __launch_bounds__(64) void ldg_k_burst_lines(
 extern "C" __global__ __launch_bounds__(64) void ldg_k_burst_field(
     const int32_t* __restrict__ smap, const double* __restrict__ video, int64_t vread_stride, int64_t vchan_stride,
     FieldRec* __restrict__ recs, double* __restrict__ lines, float* __restrict__ blevel, SysConst C, int pass,
-    const double4* __restrict__ bst) {
+    const double4* __restrict__ bst, const ReadDesc* __restrict__ reads) {
   prio_latency();
 
   __shared__ double s_c0[512], s_c1[512];
@@ -554,9 +573,18 @@ extern "C" __global__ __launch_bounds__(64) void ldg_k_burst_field(
   for (int l = lane; l < nl; l += 64) {
     lo[l] = s_lo[l];
     lvl[l] = s_lvl[l];
-    if (pass == 1) lf[l] = (s_lo[l] + 0) + c;
+    if (pass == 1) {
+      const double f = (s_lo[l] + 0) + c;
+      lf[l] = f;
+      s_lo[l] = f;                                // (this lane's own entry) for the audio guard
+    }
   }
   if (lane == 0) R->burst_group = g;
+  if (pass == 1) {
+    __syncthreads();
+    if (__syncthreads_or(audio_reach_bad(s_lo, nl, R->linecount, C, reads[slot].acut2, lane, 64)) && lane == 0)
+      R->status = FS_VCUT;
+  }
 #ifdef LDG_STAMPS
   if (blockIdx.x < KST_BLOCKS) g_kst[2][blockIdx.x][3] = __builtin_readcyclecounter();
 #endif
@@ -1094,7 +1122,8 @@ __device__ uint64_t block_kth_key(const double* a, int n, int k, int tid, int* h
 extern "C" __global__ __launch_bounds__(256) void ldg_k_pilot_field(const int32_t* __restrict__ smap,
                                                                     FieldRec* __restrict__ recs,
                                                                     double* __restrict__ lines, SysConst C,
-                                                                    double* __restrict__ scratch) {
+                                                                    double* __restrict__ scratch,
+                                                                    const ReadDesc* __restrict__ reads) {
   prio_latency();
 
   constexpr int NALL = 8192;
@@ -1140,9 +1169,14 @@ extern "C" __global__ __launch_bounds__(256) void ldg_k_pilot_field(const int32_
   const double tgt = inrange(med, 0.25, 0.75) ? .5 : 0;
   const double* ll = lines + (int64_t)slot * LINES_STRIDE + LL2 * MAX_LINES;
   double* lf = lines + (int64_t)slot * LINES_STRIDE + LLF * MAX_LINES;
+  __syncthreads();                               // s_all (the medians are done) takes the final locations
   for (int l = tid; l < nl; l += 256) {
     double v = ll[l];
     if (meta[3 * l + 0] > 0) v += (tgt - meta[3 * l + 2]) * (C.freq / 3.75) * .25;
     lf[l] = v;
+    s_all[l] = v;
   }
+  __syncthreads();
+  if (__syncthreads_or(audio_reach_bad(s_all, nl, R->linecount, C, reads[slot].acut2, tid, 256)) && tid == 0)
+    R->status = FS_VCUT;
 }

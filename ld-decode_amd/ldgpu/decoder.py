@@ -267,8 +267,10 @@ class GPUDecoder:
         # field's vsync (lddecode_core.py:926, the previous field's nextfieldoffset), so its
         # field ends ~276 NTSC / ~326 PAL lines into the read; the demod skips the video,
         # burst and pilot channels of the read's blocks past the cut below (the last ~1/4
-        # of a 1,000,001-sample read).  A field that reaches past it (a capture's first
-        # read, a jump) comes back FS_VCUT and is decoded again in full.  LDG_VCUT=0: off.
+        # of a 1,000,001-sample read), their demod_05 and, where the cut allows it (NTSC's
+        # does, native.tail_plan), the audio nothing below the cut reads.  A field that
+        # reaches past it (a capture's first read, a jump) comes back FS_VCUT and is decoded
+        # again in full.  LDG_VCUT=0: off.
         vc = os.environ.get('LDG_VCUT')
         self.video_cut = int(vc) if vc is not None else (740000 if self.sysp.name == 'NTSC' else 880000)
         self.full_keys = set()

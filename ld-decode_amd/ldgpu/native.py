@@ -25,7 +25,7 @@ EXPORTS = ['ldg_create', 'ldg_destroy', 'ldg_last_error', 'ldg_set_filters', 'ld
            'ldg_profile_read', 'ldg_synth_capture', 'ldg_capture_download', 'ldg_comb_ntsc_async', 'ldg_sync', 'ldg_demod_isolated', 'ldg_demod_isolated_ex', 'ldg_comb_set_opts', 'ldg_output_async', 'ldg_output_wait',
            'ldg_host_alloc', 'ldg_host_free',
            'ldg_archive_fields', 'ldg_archive_audio', 'ldg_decode_reads_async', 'ldg_decode_reads_async2',
-           'ldg_set_video_cut', 'ldg_decode_reads_wait',
+           'ldg_set_video_cut', 'ldg_tail_plan', 'ldg_audio_reach', 'ldg_decode_reads_wait',
            'ldg_field_audio_async', 'ldg_field_audio_collect', 'ldg_comb_ntsc3d', 'ldg_cx_create', 'ldg_cx_destroy', 'ldg_cx_process', 'ldg_comb_pal', 'ldg_comb_set_state', 'ldg_profile_spans', 'ldg_profile_spans_union', 'ldg_profile_span_table',
            'ldg_audio_offsets', 'ldg_comb_async', 'ldg_debug_rf_table',
            'ldg_stream_open', 'ldg_stream_release', 'ldg_stream_seek', 'ldg_stream_window', 'ldg_stream_stats',
@@ -169,6 +169,8 @@ def load(path=None):
     lib.ldg_decode_reads_async.argtypes = [vp, C.c_int, vp, vp, vp]
     lib.ldg_decode_reads_async2.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     lib.ldg_set_video_cut.argtypes = [vp, C.c_int64]
+    lib.ldg_tail_plan.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp]
+    lib.ldg_audio_reach.argtypes = [vp, C.c_int, C.c_int, C.c_double, vp]
     lib.ldg_decode_reads_wait.argtypes = [vp, vp]
     lib.ldg_archive_fields.argtypes = [vp, C.c_int, vp, C.c_int64]
     lib.ldg_archive_audio.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int64, vp, vp]
@@ -741,6 +743,29 @@ class Context:
         if n < 0:
             raise LDGError('ldg_capture_download -> %d' % n)
         return a[:n]
+
+
+def tail_plan(n_out, n_audio, n_audio2, vcut):
+    """ldg_tail_plan: (acut1, acut2, live audio phase-2 blocks, demod blocks making audio
+    slices, demod blocks storing demod_05) of a read under the video cut vcut (0: none);
+    acut1 / acut2 are None where the audio is not trimmed.  Host code, no device needed."""
+    out = np.zeros(5, dtype=np.int64)
+    rc = load().ldg_tail_plan(int(n_out), int(n_audio), int(n_audio2), int(vcut), out.ctypes.data)
+    if rc != 0:
+        raise ValueError('ldg_tail_plan: %d' % rc)
+    a1, a2, l2, l1, l05 = (int(v) for v in out)
+    return (None if a1 < 0 else a1, None if a2 < 0 else a2, l2, l1, l05)
+
+
+def audio_reach(lines, linecount, linelen):
+    """ldg_audio_reach: (lowest, highest) input-sample position downscale_audio can form
+    from a field's final line locations.  Host code, no device needed."""
+    ll = np.ascontiguousarray(lines, dtype=np.float64)
+    out = np.zeros(2, dtype=np.float64)
+    rc = load().ldg_audio_reach(ll.ctypes.data, ll.size, int(linecount), float(linelen), out.ctypes.data)
+    if rc != 0:
+        raise ValueError('ldg_audio_reach: %d' % rc)
+    return float(out[0]), float(out[1])
 
 
 def audio_offsets(o0, linecounts, line_period):
