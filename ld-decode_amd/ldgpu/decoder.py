@@ -782,7 +782,12 @@ class GPUDecoder:
         if len(audio):
             self.audio_offset = f.audio_next_offset
             self.transitions.append(int(f.linecount))   # offset -> next(offset, linecount)
-        vbi = self.mergevbi(fields)
+        try:
+            vbi = self.mergevbi(fields)
+        except TypeError:
+            # seconds without minutes (a lead-out code, or a lost minutes line on a CLV disc)
+            raise ReferenceCrash('mergevbi: seconds without minutes in the frame ending at read %d '
+                                 '(reference: TypeError on None * 60 * fps)' % f.readsample)
         self.vbi = vbi
         fv = f.vbi
         self.last_isclv = bool(fv['isclv'])
@@ -1010,6 +1015,7 @@ class GPUDecoder:
             eof = False
             missed = None
             window_miss = None
+            crash = None
             t0 = time.perf_counter()
             self.requested = []
             while done + len(frames) < num_frames and self._tell() + bpf * 1.05 <= size and more(nextsample):
@@ -1032,6 +1038,11 @@ class GPUDecoder:
                      self.last_read, nt, nframes_read) = cp
                     del self.transitions[nt:]
                     window_miss = WindowMiss(str(wm), resume_at=int(nextsample))
+                    break
+                except ReferenceCrash as rc:
+                    # the reference raises inside this frame: it has written the frames before it,
+                    # so this batch's go to the sink first
+                    crash = rc
                     break
                 if fr is None:
                     eof = True
@@ -1072,6 +1083,8 @@ class GPUDecoder:
             self.stats['reads_used'] += sum(len(f.field_objs) for f in frames)
             if window_miss is not None:
                 raise window_miss
+            if crash is not None:
+                raise crash
             if eof or (not frames and not launched and not self.pending):
                 break
             self._launch_wait()                 # the oldest launch: the replay continues into it

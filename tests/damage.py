@@ -52,7 +52,9 @@ class DamagedRF(SynthRF):
         self.edits = tuple((float(line), float(dur), float(ire)) for line, dur, ire in edits)
 
     def _ire(self, n):
-        ire = super()._ire(n)
+        return self._apply_edits(n, super()._ire(n))
+
+    def _apply_edits(self, n, ire):
         for line, dur, level in self.edits:
             a = (line - self.t0_lines) * self.spl
             b = a + dur * self.spl

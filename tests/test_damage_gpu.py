@@ -37,13 +37,74 @@ def _log_flags(lines):
     return fl
 
 
+def check_read(case, expect, r, inf, ctx, slot):
+    """One decoded read (ldg_field_info `inf`, debug arrays of `slot`) against the oracle's Read `r`
+    of the same samples."""
+    from ldgpu import native
+    ntsc = r.system == 'NTSC'
+    W = 910 if ntsc else 1135
+    f, start = r.field, r.start
+    assert r.outcome == expect['outcome']         # (test_damage_ref.py / test_vbi_ref.py: the capture does its job)
+    assert inf.status == _status(r.outcome), (start, r.outcome, inf.status)
+    peaks = r.crash_peaks if f is None else f.peaklist
+    assert inf.npeaks == len(peaks), start
+    assert np.array_equal(ctx.debug(slot, 41, np.int32, inf.npeaks), np.asarray(peaks)), start
+    if f is None:
+        print('%s read %d: crash' % (case, start))
+        return
+    assert inf.nvsync == len(f.vsyncs), start
+    for q in range(inf.nvsync):
+        assert list(inf.vsync[q]) == [int(x) for x in f.vsyncs[q]], (start, q)
+    assert inf.nextfieldoffset == f.nextfieldoffset, start
+    if len(peaks) >= 200:
+        assert abs(inf.med_hsync - f.med_hsync) <= 1e-12 * abs(f.med_hsync), start
+        assert abs(inf.hsync_tol - f.hsync_tolerance) <= 1e-12 * abs(f.hsync_tolerance), start
+    assert inf.log_flags == _log_flags(r.log), (start, r.log, inf.log_flags)
+    if not f.valid:
+        print('%s read %d: %s, %d peaks, %d vsyncs' % (case, start, r.outcome, inf.npeaks, inf.nvsync))
+        return
+    assert inf.istop == int(f.istop) and inf.linecount == f.linecount, start
+    for j, l in enumerate(r.rf.SysParams['philips_codelines']):
+        lc = f.linecode[l]
+        assert bool(inf.linecode_ok[j]) == (lc is not None), (start, l)
+        if lc is not None:
+            assert list(inf.linecode[j]) == [int(x) for x in lc], (start, l)
+    for k, got in (('minutes', inf.vbi_minutes), ('seconds', inf.vbi_seconds), ('clvframe', inf.vbi_clvframe),
+                   ('framenr', inf.vbi_framenr), ('status', inf.vbi_status)):
+        assert (None if got == native.VBI_NONE else int(got)) == f.vbi[k], (start, k)
+    assert bool(inf.vbi_isclv) == bool(f.vbi['isclv'])
+    nl = f.linecount + 4
+    stages = [(20, f.linelocs1), (21, f.linelocs2), (24, f.linelocs)]
+    if ntsc:
+        stages += [(22, f.linelocs3), (23, f.linelocs4)]
+    for what, arr in stages:
+        arr = np.asarray(arr, dtype=np.float64)
+        assert arr.size == nl
+        err = np.abs(ctx.debug(slot, what, np.float64, nl) - arr).max()
+        assert err < 1e-6, (start, what, err)
+    bad = np.asarray(f.linebad, dtype=bool)
+    assert np.array_equal(ctx.debug(slot, 31, np.uint8, nl).astype(bool), bad), start
+    if ntsc:
+        assert np.array_equal(ctx.debug(slot, 30, np.float32, nl), f.burstlevel), start
+    pic = ctx.debug(slot, 40, np.uint16, f.linecount * W)
+    assert pic.size == f.dspicture.size
+    d = np.abs(pic.astype(np.int64) - f.dspicture.astype(np.int64))
+    assert d.max() <= 1, (start, d.max())
+    pcm, counts, nxt = ctx.field_audio([slot], [0.0])
+    assert counts[0] * 2 == f.dsaudio.size
+    da = np.abs(pcm[0, :2 * counts[0]].astype(np.int64) - f.dsaudio.astype(np.int64))
+    assert da.max() <= 1, (start, da.max())
+    assert nxt[0] == f.audio_next_offset
+    print('%s read %d: valid, %d bad lines, .tbc %d of %d samples off by 1, .pcm %d of %d' % (
+        case, start, int(bad.sum()), int((d != 0).sum()), d.size, int((da != 0).sum()), da.size))
+
+
 @pytest.mark.parametrize('case', list(D.CASES))
 def test_stage_parity(case, gpu_ctx_ntsc, gpu_ctx_pal):
     """Every read of the case: status, peaks, vsyncs, nextfieldoffset, hsync median, log flags;
     on valid fields also the VBI, every line-location stage, linebad, burst levels, the
     resampled picture and the audio.  One test per case: the contexts are session-wide, so
     every debug array is read here, right after the decode."""
-    from ldgpu import native
     c = D.CASES[case]
     ntsc = c['system'] == 'NTSC'
     data = D.capture(case)
@@ -51,63 +112,8 @@ def test_stage_parity(case, gpu_ctx_ntsc, gpu_ctx_pal):
     ctx.set_capture(data, data.size, 0, 0)
     assert len(c['reads']) <= 8
     infos = ctx.decode_reads(c['reads'], [1.0] * len(c['reads']))
-    W = 910 if ntsc else 1135
-    for slot, start in enumerate(c['reads']):
-        r = D.oracle_read(case, slot)
-        f, inf = r.field, infos[slot]
-        assert r.outcome == c['expect'][slot]['outcome']         # (test_damage_ref.py: the capture does its job)
-        assert inf.status == _status(r.outcome), (start, r.outcome, inf.status)
-        peaks = r.crash_peaks if f is None else f.peaklist
-        assert inf.npeaks == len(peaks), start
-        assert np.array_equal(ctx.debug(slot, 41, np.int32, inf.npeaks), np.asarray(peaks)), start
-        if f is None:
-            print('%s read %d: crash' % (case, start))
-            continue
-        assert inf.nvsync == len(f.vsyncs), start
-        for q in range(inf.nvsync):
-            assert list(inf.vsync[q]) == [int(x) for x in f.vsyncs[q]], (start, q)
-        assert inf.nextfieldoffset == f.nextfieldoffset, start
-        if len(peaks) >= 200:
-            assert abs(inf.med_hsync - f.med_hsync) <= 1e-12 * abs(f.med_hsync), start
-            assert abs(inf.hsync_tol - f.hsync_tolerance) <= 1e-12 * abs(f.hsync_tolerance), start
-        assert inf.log_flags == _log_flags(r.log), (start, r.log, inf.log_flags)
-        if not f.valid:
-            print('%s read %d: %s, %d peaks, %d vsyncs' % (case, start, r.outcome, inf.npeaks, inf.nvsync))
-            continue
-        assert inf.istop == int(f.istop) and inf.linecount == f.linecount, start
-        for j, l in enumerate(r.rf.SysParams['philips_codelines']):
-            lc = f.linecode[l]
-            assert bool(inf.linecode_ok[j]) == (lc is not None), (start, l)
-            if lc is not None:
-                assert list(inf.linecode[j]) == [int(x) for x in lc], (start, l)
-        for k, got in (('minutes', inf.vbi_minutes), ('seconds', inf.vbi_seconds), ('clvframe', inf.vbi_clvframe),
-                       ('framenr', inf.vbi_framenr), ('status', inf.vbi_status)):
-            assert (None if got == native.VBI_NONE else int(got)) == f.vbi[k], (start, k)
-        assert bool(inf.vbi_isclv) == bool(f.vbi['isclv'])
-        nl = f.linecount + 4
-        stages = [(20, f.linelocs1), (21, f.linelocs2), (24, f.linelocs)]
-        if ntsc:
-            stages += [(22, f.linelocs3), (23, f.linelocs4)]
-        for what, arr in stages:
-            arr = np.asarray(arr, dtype=np.float64)
-            assert arr.size == nl
-            err = np.abs(ctx.debug(slot, what, np.float64, nl) - arr).max()
-            assert err < 1e-6, (start, what, err)
-        bad = np.asarray(f.linebad, dtype=bool)
-        assert np.array_equal(ctx.debug(slot, 31, np.uint8, nl).astype(bool), bad), start
-        if ntsc:
-            assert np.array_equal(ctx.debug(slot, 30, np.float32, nl), f.burstlevel), start
-        pic = ctx.debug(slot, 40, np.uint16, f.linecount * W)
-        assert pic.size == f.dspicture.size
-        d = np.abs(pic.astype(np.int64) - f.dspicture.astype(np.int64))
-        assert d.max() <= 1, (start, d.max())
-        pcm, counts, nxt = ctx.field_audio([slot], [0.0])
-        assert counts[0] * 2 == f.dsaudio.size
-        da = np.abs(pcm[0, :2 * counts[0]].astype(np.int64) - f.dsaudio.astype(np.int64))
-        assert da.max() <= 1, (start, da.max())
-        assert nxt[0] == f.audio_next_offset
-        print('%s read %d: valid, %d bad lines, .tbc %d of %d samples off by 1, .pcm %d of %d' % (
-            case, start, int(bad.sum()), int((d != 0).sum()), d.size, int((da != 0).sum()), da.size))
+    for slot in range(len(c['reads'])):
+        check_read(case, c['expect'][slot], D.oracle_read(case, slot), infos[slot], ctx, slot)
 
 
 def _decode(dec):
