@@ -360,6 +360,49 @@ int ldg_conceal_frames(ldg_ctx* ctx, int n, uint16_t* frames, const int16_t* run
  * and its calls: up to n of these four doubles.  Returns the count written. */
 int ldg_stack_stats(ldg_ctx* ctx, double* out, int n);
 
+/* ---- EFM run lengths (BUILD-DEFINED: the reference snapshot has none) ----
+ * The digital-audio signal below 2 MHz of the same RF, as the run lengths between its zero
+ * crossings in channel bits (3..11), one byte each: the content of a .efm file.  The raw samples
+ * are low-passed (255 taps) and decimated by 4, a 57.6 us centred mean is removed, the zero
+ * crossings are timed by linear interpolation, and a first-order clock loop per segment of
+ * 2^20 RF samples (started 2^16 samples early) counts the channel bits between them.  All
+ * indices are RF samples / segments of the whole capture file. */
+typedef struct ldg_efm_opts {
+  double fs;          /* RF sample rate (40e6); the channel clock is 4 321 800 Hz  */
+  double alpha, beta; /* loop gains: phase, period                                  */
+  double delta;       /* the period stays within 1 -+ delta of nominal              */
+  int32_t keep_debug; /* != 0: keep z for ldg_efm_debug_read                        */
+  int32_t pad_;
+} ldg_efm_opts;
+typedef struct ldg_efm_seg {
+  int64_t emitted;      /* bytes written for the segment                            */
+  int64_t ignored;      /* own crossings less than half a channel bit after the loop's reference */
+  int64_t clamped_low;  /* emitted run lengths below 3 written as 3                 */
+  int64_t clamped_high; /* above 11 written as 11                                   */
+  double final_P;       /* the loop's period (RF samples per channel bit) at the segment's end */
+} ldg_efm_seg;
+/* fs 40e6, alpha 0.1, beta 0.002, delta 0.03, keep_debug 0.  Host code, no context. */
+int ldg_efm_defaults(ldg_efm_opts* out);
+/* The options and the ntaps == 255 low-pass taps (firwin(255, 1.75 MHz) at 40 MHz) for later
+ * ldg_efm_extract calls; allocates the EFM state of the context. */
+int ldg_efm_set_opts(ldg_ctx* ctx, const ldg_efm_opts* opts, const double* taps, int ntaps);
+/* out[0], out[1]: the samples [lo, hi) of a file of file_nsamples samples that segments
+ * [seg_lo, seg_hi) read (run-in, filter and baseline reach included), clipped to the file; lo is
+ * a multiple of 12 (whole .r30 and .lds groups).  0, 0: nothing.  Host code, no context. */
+int ldg_efm_window(int64_t seg_lo, int64_t seg_hi, int64_t file_nsamples, int64_t out[2]);
+/* The bytes of segments [seg_lo, seg_hi) in order.  raw: nbytes of the file in format fmt from
+ * sample first_sample (on a packing group), host or device memory, covering at least
+ * ldg_efm_window's range (LDG_EINVAL otherwise).  out holds cap bytes (a segment range emits at
+ * most (seg_hi - seg_lo) * 2^18 + 2^14); *n_out the bytes written (on LDG_EINVAL for a small cap:
+ * the bytes needed); per_segment [seg_hi - seg_lo].  Synchronous, on a stream of its own; at most
+ * 65535 segments a call.  Its kernels report through ldg_profile_read as efm_*. */
+int ldg_efm_extract(ldg_ctx* ctx, const void* raw, int64_t nbytes, int fmt, int64_t first_sample, int64_t file_nsamples,
+                    int64_t seg_lo, int64_t seg_hi, uint8_t* out, int64_t cap, int64_t* n_out, ldg_efm_seg* per_segment);
+/* Parity access to the last ldg_efm_extract: what 0: z [float64] (keep_debug only, LDG_ESTATE
+ * otherwise), *first the decimated index m of its first value; 1: the crossing times [float64] in
+ * order, *first 0.  Copies up to cap bytes to dst; returns the bytes copied or an error. */
+int64_t ldg_efm_debug_read(ldg_ctx* ctx, int what, void* dst, int64_t cap, int64_t* first);
+
 /* Debug / parity access to the per-read device arrays of a live slot.
  * what: 0..4 demod channels (demod, demod_05, demod_sync, demod_burst, demod_pilot)
  *       [float64, n_out] (demod_05, demod_sync and demod_burst are expanded on request from

@@ -11,7 +11,8 @@ and the same outputs: <outfile>.tbc (native uint16 frames) and <outfile>.pcm
 (int16 stereo, 48 kHz); cut mode (-c) writes <outfile>.r16.  Additions:
 <outfile>.json (per-frame VBI and per-field metadata, one JSON list) and
 --comb (<outfile>.rgb: comb-ntsc's default rgb48 744x480 frames; --comb-3d:
-comb-ntsc -d 3 -F's).  The comb alone, on a .tbc stream: comb_ntsc.py.
+comb-ntsc -d 3 -F's).  The comb alone, on a .tbc stream: comb_ntsc.py.  --efm adds
+<outfile>.efm (the EFM digital-audio run lengths, as efm_extract.py writes them).
 """
 import argparse
 import json
@@ -119,6 +120,10 @@ def parse(argv=None):
                    help='samples below this level are flagged (default: the sync tip - 50 IRE)')
     p.add_argument('--dropout-hi-ire', type=float, default=None,
                    help='samples above this level are flagged (default 150 IRE)')
+    p.add_argument('--efm', action='store_true',
+                   help='after the decode, write the EFM (digital audio) run lengths of the samples it consumed to '
+                        '<outfile>.efm and a summary to <outfile>.efm.json (build-defined rule, DESIGN.md section 7c; '
+                        'the same as efm_extract.py over that range); one process, no epochs, not with -c')
     p.add_argument('--no-json', action='store_true', help='do not write <outfile>.json')
     p.add_argument('--stats-json', default=None,
                    help='one process: write a timing breakdown of the run (read, decode, write) to this file')
@@ -150,6 +155,10 @@ def main(argv=None):
         return 1
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
+    if args.efm and (world > 1 or args.epoch_frames or args.manifest or args.cut):
+        print("ERROR: --efm is a second pass of one plain decode: not with sharding (WORLD_SIZE > 1), "
+              "--epoch-frames / --manifest or -c; run efm_extract.py on the capture instead")
+        return 1
     rccl = False
     if world > 1:
         # one process per GPU (python -m torch.distributed.run --nproc-per-node N lddecode.py ...):
@@ -293,6 +302,17 @@ def main(argv=None):
     t_all = time.perf_counter() - t0
     if args.stats_json:
         write_stats(args.stats_json, dec, n, meta_all, t_dec, t_all, w, w_rgb)
+    if args.efm:
+        # a second pass over the samples the decode consumed (first read .. last nextsample);
+        # the file is read again, from the page cache where it fits
+        from ldgpu import efm
+        t1 = time.perf_counter()
+        first = meta_all[0]['fields'][0]['readsample'] if meta_all else nextsample
+        last = meta_all[-1]['nextsample'] if meta_all else nextsample
+        summ = efm.extract_file(dec.ctx, filename, outname, first, last, fmt=fmt)
+        print('efm: %d run lengths from samples [%d, %d), %d of %d syncs 588 bits apart, %.2f s' % (
+            summ['run_lengths'], summ['samples'][0], summ['samples'][1], summ['frames_588'],
+            max(summ['syncs'] - 1, 0), time.perf_counter() - t1))
     return 0
 
 

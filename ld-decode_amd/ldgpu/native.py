@@ -31,7 +31,8 @@ EXPORTS = ['ldg_create', 'ldg_destroy', 'ldg_last_error', 'ldg_set_filters', 'ld
            'ldg_stream_open', 'ldg_stream_release', 'ldg_stream_seek', 'ldg_stream_window', 'ldg_stream_stats',
            'ldg_stream_close', 'ldg_device_memory',
            'ldg_dropout_defaults', 'ldg_set_dropout_opts', 'ldg_field_dropouts',
-           'ldg_stack_frames', 'ldg_conceal_frames', 'ldg_stack_stats']
+           'ldg_stack_frames', 'ldg_conceal_frames', 'ldg_stack_stats',
+           'ldg_efm_defaults', 'ldg_efm_set_opts', 'ldg_efm_window', 'ldg_efm_extract', 'ldg_efm_debug_read']
 STACK_MAX_SOURCES = 16            # LDG_STACK_MAX_SOURCES
 STACK_MODES = {'median': 0, 'mean': 1, 'smart-mean': 2}      # LDG_STACK_*
 STACK_STATS = ('h2d_s', 'kernel_s', 'd2h_s', 'calls')        # ldg_stack_stats, in order
@@ -97,6 +98,40 @@ class DropoutOpts(C.Structure):
 class Dropout(C.Structure):
     """ldg_dropout: pixels [startx, endx) of field row `row`."""
     _fields_ = [('row', C.c_int16), ('startx', C.c_int16), ('endx', C.c_int16), ('pad_', C.c_int16)]
+
+
+class EfmOpts(C.Structure):
+    """ldg_efm_opts (include/ldgpu.h): the build-defined EFM run-length extraction's options."""
+    _fields_ = [('fs', C.c_double), ('alpha', C.c_double), ('beta', C.c_double), ('delta', C.c_double),
+                ('keep_debug', C.c_int32), ('pad_', C.c_int32)]
+
+
+class EfmSeg(C.Structure):
+    """ldg_efm_seg: one segment's counters."""
+    _fields_ = [('emitted', C.c_int64), ('ignored', C.c_int64), ('clamped_low', C.c_int64),
+                ('clamped_high', C.c_int64), ('final_P', C.c_double)]
+
+
+EFM_SEG = 1 << 20                 # RF samples per EFM segment (csrc/efm_plan.hpp SEG)
+EFM_NTAPS = 255
+EFM_CHANNEL_HZ = 4321800.0
+
+
+def efm_defaults():
+    """ldg_efm_defaults as a dict (keys of ldg_efm_opts); no device needed."""
+    o = EfmOpts()
+    if load().ldg_efm_defaults(C.byref(o)) != LDG_OK:
+        raise LDGError('ldg_efm_defaults failed')
+    return {k: getattr(o, k) for k, _ in EfmOpts._fields_ if k != 'pad_'}
+
+
+def efm_window(seg_lo, seg_hi, file_nsamples):
+    """ldg_efm_window: the samples [lo, hi) of the file that segments [seg_lo, seg_hi) read
+    ((0, 0): none).  Host code, no device needed."""
+    out = np.zeros(2, dtype=np.int64)
+    if load().ldg_efm_window(int(seg_lo), int(seg_hi), int(file_nsamples), out.ctypes.data) != LDG_OK:
+        raise ValueError('ldg_efm_window: invalid segment range (%r, %r, %r)' % (seg_lo, seg_hi, file_nsamples))
+    return int(out[0]), int(out[1])
 
 
 def dropout_defaults(system):
@@ -205,6 +240,13 @@ def load(path=None):
     lib.ldg_stack_frames.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, vp]
     lib.ldg_conceal_frames.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     lib.ldg_stack_stats.argtypes = [vp, vp, C.c_int]
+    lib.ldg_efm_defaults.argtypes = [C.POINTER(EfmOpts)]
+    lib.ldg_efm_set_opts.argtypes = [vp, C.POINTER(EfmOpts), vp, C.c_int]
+    lib.ldg_efm_window.argtypes = [C.c_int64, C.c_int64, C.c_int64, vp]
+    lib.ldg_efm_extract.argtypes = [vp, vp, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp,
+                                    C.c_int64, C.POINTER(C.c_int64), vp]
+    lib.ldg_efm_debug_read.argtypes = [vp, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64)]
+    lib.ldg_efm_debug_read.restype = C.c_int64
     lib.ldg_version.restype = C.c_char_p
     lib.ldg_device_count.restype = C.c_int
     _lib = lib
@@ -678,6 +720,55 @@ class Context:
         if n < 0:
             self._check(n, 'ldg_stack_stats')
         return dict(zip(STACK_STATS[:n], (float(x) for x in out[:n])))
+
+    # ---- EFM run lengths (build-defined; include/ldgpu.h) --------
+    def efm_set_opts(self, taps, **opts):
+        """ldg_efm_set_opts: the 255 low-pass taps and ldg_efm_opts fields over the defaults.
+        Returns the options in force."""
+        o = efm_defaults()
+        for k, v in opts.items():
+            if k not in o:
+                raise TypeError('unknown EFM option %s' % k)
+            o[k] = v
+        c = EfmOpts(float(o['fs']), float(o['alpha']), float(o['beta']), float(o['delta']), int(bool(o['keep_debug'])), 0)
+        t = np.ascontiguousarray(taps, dtype=np.float64)
+        self._check(self.lib.ldg_efm_set_opts(self.h, C.byref(c), t.ctypes.data, t.size), 'ldg_efm_set_opts')
+        return o
+
+    def efm_extract(self, raw, fmt, first_sample, file_nsamples, seg_lo, seg_hi, device_ptr=None, nbytes=None):
+        """ldg_efm_extract: (bytes uint8[n], per-segment list of dicts).  raw: the window's bytes
+        (buffer or uint8 array) from first_sample; or device_ptr / nbytes for a window in HBM."""
+        nseg = max(int(seg_hi) - int(seg_lo), 0)
+        cap = nseg * (EFM_SEG // 4) + (1 << 14)
+        out = np.empty(cap, dtype=np.uint8)
+        segs = (EfmSeg * max(nseg, 1))()
+        n = C.c_int64(0)
+        if device_ptr is not None:
+            ptr, nb = C.c_void_p(device_ptr), int(nbytes)
+        else:
+            buf = np.frombuffer(raw, dtype=np.uint8) if not isinstance(raw, np.ndarray) else raw.view(np.uint8)
+            buf = np.ascontiguousarray(buf)
+            ptr, nb = buf.ctypes.data_as(C.c_void_p), buf.size
+        self._check(self.lib.ldg_efm_extract(self.h, ptr, nb, int(fmt), int(first_sample), int(file_nsamples),
+                                             int(seg_lo), int(seg_hi), out.ctypes.data, cap, C.byref(n), segs),
+                    'ldg_efm_extract')
+        return out[:n.value].copy(), [{k: getattr(segs[i], k) for k, _ in EfmSeg._fields_} for i in range(nseg)]
+
+    def efm_debug(self, what):
+        """ldg_efm_debug_read of the last efm_extract: 'z' -> (first m, float64 z), 'times' ->
+        float64 crossing times."""
+        w = {'z': 0, 'times': 1}[what]
+        first = C.c_int64(0)
+        a = np.zeros(1 << 16, dtype=np.float64)
+        while True:
+            rc = self.lib.ldg_efm_debug_read(self.h, w, a.ctypes.data, a.nbytes, C.byref(first))
+            if rc < 0:
+                raise LDGError('ldg_efm_debug_read(%s) -> %d' % (what, rc))
+            if rc < a.nbytes:
+                break
+            a = np.zeros(a.size * 4, dtype=np.float64)
+        a = a[:rc // 8].copy()
+        return (int(first.value), a) if what == 'z' else a
 
     # ---- profiling / tooling -------------------------------------------------------
     def profile(self, on=True):
