@@ -412,7 +412,14 @@ int64_t ldg_efm_debug_read(ldg_ctx* ctx, int what, void* dst, int64_t cap, int64
  *       50: the last ldg_comb_ntsc[3d] call's burst-level EMA per line (lines 38..524 of each
  *       frame) [float64]; 51: the comb's carried EMA state [float64] (50 and 51 ignore `slot`);
  *       60: the slot's raw dropout runs as the last ldg_field_dropouts over it left them
- *       [int16, 320 rows x 8 x (startx, endx)]; 61: their per-row counts [int32, 320].
+ *       [int16, 320 rows x 8 x (startx, endx)]; 61: their per-row counts [int32, 320];
+ *       70..75: the optical flow's buffers (3D comb with opticalflow) for the last frame that took
+ *       the flow path: 70 its luma fields [uint16, 2 x 252 x 840]; 71, 72, 73 its polynomial
+ *       expansions at pyramid levels 0, 1, 2 [float64, 2 x h x w x 5 with h x w = 252 x 840,
+ *       126 x 420, 63 x 210]; 74 the level-0 flow (x, y) [float64, 2 x 252 x 840 x 2]; 75 the
+ *       weight map that flow gave [float64, 252 x 840].  They ignore `slot`, synchronise the
+ *       device, and return LDG_EINVAL until a frame has taken the flow path since the context's
+ *       creation or the last ldg_comb_reset (70..73: the comb's second frame; 74, 75: its third).
  * Copies up to `cap` bytes to host `dst`; returns bytes copied (>= 0) or an error. */
 int64_t ldg_debug_read(ldg_ctx* ctx, int slot, int what, void* dst, int64_t cap);
 

@@ -277,6 +277,7 @@ struct ldg_ctx {
     double* cv2d = nullptr;                    // one frame's 2D chroma rows
     double* kmap = nullptr;                    // weight maps by window slot, [2 + max_frames][FR][FC]
     int rcur = 0;
+    int klast = 0;                             // kmap slot of the last flow's weight map (debug read-back)
     int64_t frames = 0;                        // frames the comb has seen (Process calls)
   } of;
   uint16_t* comb_in = nullptr;
@@ -2483,8 +2484,9 @@ static int flow_frame(ldg_ctx* ctx, hipStream_t st, const uint16_t* fr, int slot
                         F.M);
       }
     }
+    F.klast = slot - 1;
     LDG_LAUNCH_ON(st, "flow_combk", ldg_k_flow_combk, flow::FR, 256, F.fl[0], core, range,
-                  F.kmap + (size_t)(slot - 1) * flow::FR * flow::FC);
+                  F.kmap + (size_t)F.klast * flow::FR * flow::FC);
   }
   F.rcur ^= 1;
   return check_launch(ctx, "flow kernels");
@@ -2614,6 +2616,33 @@ int64_t ldg_debug_read(ldg_ctx* ctx, int slot, int what, void* dst, int64_t cap)
     if (bytes > cap) bytes = cap;
     if (hipMemcpy(dst, what == 50 ? ctx->comb_abl : ctx->comb_state, bytes, hipMemcpyDeviceToHost) != hipSuccess)
       return LDG_EDEVICE;
+    return bytes;
+  }
+  if (ctx && dst && what >= 70 && what <= 75) {
+    // the optical flow's buffers for the last frame that took the flow path (flow_frame): 70 its luma
+    // fields, 71..73 its expansions at levels 0..2, 74 the level-0 flow, 75 the weight map that flow wrote
+    const auto& F = ctx->of;
+    if (!F.ybuf || F.frames < (what >= 74 ? 3 : 2)) return LDG_EINVAL;
+    if (hipSetDevice(ctx->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return LDG_EDEVICE;
+    const int64_t px = (int64_t)flow::FR * flow::FC;
+    const void* src = nullptr;
+    int64_t bytes = 0;
+    if (what == 70) {
+      src = F.ybuf;
+      bytes = 2 * px * 2;
+    } else if (what <= 73) {
+      const int k = what - 71;
+      src = F.R[F.rcur ^ 1][k];                // flow_frame flips rcur once the frame is done
+      bytes = (int64_t)2 * kFlowH[k] * kFlowW[k] * 5 * 8;
+    } else if (what == 74) {
+      src = F.fl[0];
+      bytes = 2 * px * 2 * 8;
+    } else {
+      src = F.kmap + (int64_t)F.klast * px;
+      bytes = px * 8;
+    }
+    if (bytes > cap) bytes = cap;
+    if (hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) != hipSuccess) return LDG_EDEVICE;
     return bytes;
   }
   if (!ctx || !dst || slot < 0 || slot >= ctx->max_reads || !ctx->live[slot]) return LDG_EINVAL;

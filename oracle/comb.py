@@ -116,12 +116,17 @@ class Comb3DFlow:
     g = 2 the flow against the previous frame's (the last flow as the initial estimate from
     g = 3) and the weight map of frame g - 1, which is then output (clp2 = frame g -
     frame g - 1): nothing for the first two inputs, one frame late, never the last.  The
-    flow path raises the Y / C noise-reduction clips to 4 (raw) from the second frame."""
+    flow path raises the Y / C noise-reduction clips to 4 (raw) from the second frame.
+    For the per-stage tests the last frame's luma fields (`fields`), flows (`flow`) and field
+    weight map (`weight`, 252 x 840) stay readable, and with keep_history every input frame
+    appends a dict of the three (None where the frame has none yet) to `history`."""
 
-    def __init__(self, core_ire=-1.0, range_ire=-1.0, **opts):
+    def __init__(self, core_ire=-1.0, range_ire=-1.0, keep_history=False, **opts):
         self.lib = _load()
         self.h = self.lib.comb2d_create()
         self.opts = _set_opts(self.lib.comb2d_set_opts, self.h, opts)
+        self.fields, self.weight = None, None
+        self.history = [] if keep_history else None
         # comb-ntsc main() with flow: p_3dcore / p_3drange 0 / 0.5 IRE by default, times irescale
         self.core = (0.0 if core_ire < 0 else core_ire) * 358.4
         self.range = (0.5 if range_ire < 0 else range_ire) * 358.4
@@ -155,11 +160,14 @@ class Comb3DFlow:
                     init = self.flow if g >= 3 else [None, None]
                     self.flow = [farneback(cur[k], self.prev_fields[k], init[k]) for k in range(2)]
                     km = np.ascontiguousarray(combk_from_flow(self.flow[0], self.flow[1], self.core, self.range))
+                    self.weight = km[0:2 * cur.shape[1]:2, 70:70 + cur.shape[2]].copy()
                     out = np.zeros((self.opts['linesout'], W, 3), dtype=np.uint16)
                     self.lib.comb2d_process_of(self.h, self.held.ctypes.data, fr.ctypes.data, km.ctypes.data,
                                                out.ctypes.data)
                     outs.append(out)
-                self.prev_fields = cur
+                self.prev_fields = self.fields = cur
+            if self.history is not None:
+                self.history.append(dict(fields=self.fields, flow=self.flow, weight=self.weight))
             self.held = np.ascontiguousarray(fr)
         return np.stack(outs) if outs else np.zeros((0, self.opts['linesout'], W, 3), dtype=np.uint16)
 

@@ -245,24 +245,46 @@ def update_flow(M, block_size=WINSIZE):
     return flow
 
 
-def farneback(prev0, next0, flow0=None):
-    """calcOpticalFlowFarneback(prev0, next0, flow0, 0.5, 4, 60, 3, 7, 1.5,
-    OPTFLOW_USE_INITIAL_FLOW if flow0 is given): the flow (h, w, 2) in pixels, float64."""
-    img = [np.asarray(prev0, dtype=np.float64), np.asarray(next0, dtype=np.float64)]
-    H, W = img[0].shape
+def pyramid_levels(H, W):
+    """The number of pyramid levels below the image the flow uses (the 32-pixel minimum)."""
     scale, levels = 1.0, 0
     for k in range(LEVELS):
         scale *= PYR_SCALE
         if W * scale < MIN_SIZE or H * scale < MIN_SIZE:
             break
         levels = k + 1
+    return levels
+
+
+def level_params(k, H, W):
+    """Pyramid level k of an H x W image: (scale, sigma and size of its Gaussian blur, w, h)."""
+    scale = PYR_SCALE ** k
+    sigma = (1.0 / scale - 1) * 0.5
+    smooth = max(cv_round(sigma * 5) | 1, 3)
+    return scale, sigma, smooth, cv_round(W * scale), cv_round(H * scale)
+
+
+def expansion(img, k):
+    """The polynomial expansion (h, w, 5) of one image at pyramid level k, as farneback()
+    computes it: GaussianBlur -> resize(INTER_LINEAR) (level 0: none) -> FarnebackPolyExp."""
+    img = np.asarray(img, dtype=np.float64)
+    H, W = img.shape
+    _, sigma, smooth, w, h = level_params(k, H, W)
+    f = gaussian_blur(img, smooth, sigma)
+    I = f if (w, h) == (W, H) else resize_linear(f, w, h)
+    return poly_exp(I)
+
+
+def farneback(prev0, next0, flow0=None):
+    """calcOpticalFlowFarneback(prev0, next0, flow0, 0.5, 4, 60, 3, 7, 1.5,
+    OPTFLOW_USE_INITIAL_FLOW if flow0 is given): the flow (h, w, 2) in pixels, float64."""
+    img = [np.asarray(prev0, dtype=np.float64), np.asarray(next0, dtype=np.float64)]
+    H, W = img[0].shape
+    levels = pyramid_levels(H, W)
     prev_flow = None
     flow = None
     for k in range(levels, -1, -1):
-        scale = PYR_SCALE ** k
-        sigma = (1.0 / scale - 1) * 0.5
-        smooth = max(cv_round(sigma * 5) | 1, 3)
-        w, h = cv_round(W * scale), cv_round(H * scale)
+        scale, _, _, w, h = level_params(k, H, W)
         if prev_flow is None:
             if flow0 is not None:
                 flow = resize_area_int(np.asarray(flow0, dtype=np.float64), w, h) * scale
@@ -270,11 +292,7 @@ def farneback(prev0, next0, flow0=None):
                 flow = np.zeros((h, w, 2))
         else:
             flow = resize_linear(prev_flow, w, h) * (1.0 / PYR_SCALE)
-        R = []
-        for i in range(2):
-            f = gaussian_blur(img[i], smooth, sigma)
-            I = f if (w, h) == (W, H) else resize_linear(f, w, h)
-            R.append(poly_exp(I))
+        R = [expansion(img[i], k) for i in range(2)]
         M = update_matrices(R[0], R[1], flow)
         for it in range(ITERATIONS):
             flow = update_flow(M)
@@ -302,15 +320,20 @@ def field_images(ybuf):
     return out
 
 
-def combk_from_flow(flow0, flow1, core, rng):
-    """OpticalFlow3D's 3D weight (comb-ntsc.cxx:633-650): per field pixel
+def field_weight(flow0, flow1, core, rng):
+    """OpticalFlow3D's 3D weight per field pixel (comb-ntsc.cxx:633-650):
     c = 1 - clamp((|(fy, 2 fx)| - core) / range, 0, 1) (core / range the -c / -r values
-    times irescale), the smaller of the two fields', for frame rows 2 y and 2 y + 1 at
-    columns 70..909 of a 525 x 910 map (0 elsewhere)."""
+    times irescale), the smaller of the two fields' (252 x 840)."""
     def c_of(fl):
         r = np.sqrt(fl[..., 1] * fl[..., 1] + (fl[..., 0] * 2) * (fl[..., 0] * 2))
         return 1 - np.clip((r - core) / rng, 0, 1)
-    c = np.minimum(c_of(flow0), c_of(flow1))
+    return np.minimum(c_of(flow0), c_of(flow1))
+
+
+def combk_from_flow(flow0, flow1, core, rng):
+    """field_weight() as combk[2]: for frame rows 2 y and 2 y + 1 at columns 70..909 of a
+    525 x 910 map (0 elsewhere)."""
+    c = field_weight(flow0, flow1, core, rng)
     k = np.zeros((525, 910))
     k[0:2 * FIELD_ROWS:2, FIELD_X0:FIELD_X0 + FIELD_COLS] = c
     k[1:2 * FIELD_ROWS:2, FIELD_X0:FIELD_X0 + FIELD_COLS] = c
