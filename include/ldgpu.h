@@ -403,6 +403,52 @@ int ldg_efm_extract(ldg_ctx* ctx, const void* raw, int64_t nbytes, int fmt, int6
  * order, *first 0.  Copies up to cap bytes to dst; returns the bytes copied or an error. */
 int64_t ldg_efm_debug_read(ldg_ctx* ctx, int what, void* dst, int64_t cap, int64_t* first);
 
+/* ---- EFM decode (BUILD-DEFINED: the reference snapshot has the code table and no decoder;
+ * DESIGN.md section 7d) ----
+ * The run lengths of a .efm stream to 44.1 kHz stereo PCM: a frame grid from the sync patterns
+ * (11, 11) confirmed at +-588 channel bits, 33 symbols a frame through the inverse code table,
+ * C1 (one error), the delay lines, C2 (two errors, or up to four erasures), the sample map and
+ * a stateless concealment.  All integers.  The stream is fed in calls of any size; the result
+ * does not depend on how it is cut. */
+typedef struct ldg_efmdec_info { /* one ldg_efmdec_feed; counters are this call's share */
+  int64_t first_frame, frames;   /* the frames this call added, indexed from the stream's first */
+  int64_t first_sample, samples; /* the stereo samples it emitted                               */
+  int64_t candidates, confirmed; /* sync patterns; those with another at +-588                  */
+  int64_t coasted, breaks;       /* frames started without a sync of their own; gaps > 7350 frames */
+  int64_t bad_symbols;           /* data symbols that are no code word (decoded as 0)           */
+  int64_t c1_pass, c1_fixed, c1_erased;
+  int64_t c2_pass, c2_fixed, c2_erasure_solved, c2_failed, c2_unsolved; /* unsolved: > 4 erasures, passed through */
+  int64_t flagged, averaged, muted; /* samples x channels                                       */
+  int64_t held_runs;             /* run lengths kept for the next call                          */
+} ldg_efmdec_info;
+/* The 16384-entry inverse of the code table: 0..255 a value, 0x100 / 0x101 the subcode syncs S0 /
+ * S1, 0xFFFF no code word.  Allocates the decode state of the context and resets the stream. */
+int ldg_efmdec_set_table(ldg_ctx* ctx, const uint16_t* inverse, int n);
+/* Forgets the stream: the next ldg_efmdec_feed starts at its first transition. */
+int ldg_efmdec_reset(ldg_ctx* ctx);
+/* The next n run lengths (host memory; channel bits between transitions, a byte each).  final != 0
+ * ends the stream: the last confirmed sync starts a frame and everything held is emitted.
+ * Synchronous, on a stream of its own; its kernels report through ldg_profile_read as efmdec_*.
+ * After an error the stream is undefined until ldg_efmdec_reset. */
+int ldg_efmdec_feed(ldg_ctx* ctx, const uint8_t* rl, int64_t n, int final, ldg_efmdec_info* info);
+/* What the last ldg_efmdec_feed produced.  *first: the stereo sample (PCM, FLAGS) or frame (the
+ * others) of the first element.  PCM [int16, samples x 2, left first], FLAGS [uint8, samples x 2],
+ * SUBCODE [uint16 per frame], and for parity: STARTS [int64 per frame, channel bits from the
+ * stream's first transition], F3 [uint8, 32 per frame], C1 [uint8, 28 per frame] and C1_FLAGS
+ * [uint8 per frame: erased], C2 [uint8, 28 per frame] and C2_FLAGS [uint32 per frame: bit j
+ * flags symbol j]; C1 / C2 rows of frames without a word (frame 0; below 109) are zeros.  Copies up
+ * to cap bytes to dst; returns the bytes copied or an error. */
+#define LDG_EFMDEC_PCM 0
+#define LDG_EFMDEC_FLAGS 1
+#define LDG_EFMDEC_SUBCODE 2
+#define LDG_EFMDEC_STARTS 10
+#define LDG_EFMDEC_F3 11
+#define LDG_EFMDEC_C1 12
+#define LDG_EFMDEC_C1_FLAGS 13
+#define LDG_EFMDEC_C2 14
+#define LDG_EFMDEC_C2_FLAGS 15
+int64_t ldg_efmdec_read(ldg_ctx* ctx, int what, void* dst, int64_t cap, int64_t* first);
+
 /* Debug / parity access to the per-read device arrays of a live slot.
  * what: 0..4 demod channels (demod, demod_05, demod_sync, demod_burst, demod_pilot)
  *       [float64, n_out] (demod_05, demod_sync and demod_burst are expanded on request from

@@ -52,6 +52,7 @@ static inline bool comb_is_default(const comb::CombOpt& o) {
 
 struct CapStream;                 // stream.inc: a capture streamed from its file through an HBM ring
 struct ldg_efm_state;             // efm.inc: the EFM run-length extraction's options and buffers
+struct ldg_efmdec_state;          // efmdec.inc: the EFM decode's table, carried stream and buffers
 
 struct ldg_ctx {
   int device = 0;
@@ -229,6 +230,7 @@ struct ldg_ctx {
   uint32_t* d_stack_rowinfo = nullptr;   // [max_frames][625]: StackArgs::rowinfo
   double stack_t[4] = {};          // ldg_stack_stats: seconds H2D, kernel, D2H; calls
   ldg_efm_state* efm = nullptr;    // EFM run lengths (efm.hip), allocated by ldg_efm_set_opts
+  ldg_efmdec_state* efmdec = nullptr;   // EFM decode (efmdec.hip), allocated by ldg_efmdec_set_table
   hipEvent_t ev_fbuf[2] = {nullptr, nullptr};
   bool fbuf_recorded[2] = {false, false};
   hipEvent_t ev_tbc = nullptr;
@@ -685,6 +687,7 @@ int ldg_create(const ldg_config* cfg, ldg_ctx** out) {
 static void arch_audio_free(ldg_ctx* ctx);
 static void stack_free(ldg_ctx* ctx);
 static void efm_free(ldg_ctx* ctx);   // efm.inc
+static void efmdec_free(ldg_ctx* ctx);   // efmdec.inc
 
 int ldg_destroy(ldg_ctx* ctx) {
   if (!ctx) return LDG_EINVAL;
@@ -731,6 +734,7 @@ int ldg_destroy(ldg_ctx* ctx) {
   if (ctx->h_drop) (void)hipHostFree(ctx->h_drop);
   stack_free(ctx);
   efm_free(ctx);
+  efmdec_free(ctx);
   if (ctx->cap_owned) dfree(ctx->cap);
 
   for (void* p : {(void*)ctx->comb_state, (void*)ctx->comb_abl, (void*)ctx->comb_in, (void*)ctx->comb_rgb,

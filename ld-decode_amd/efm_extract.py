@@ -5,8 +5,8 @@
                                         [--stats] capture out
 
 Writes <out>.efm -- one byte per run length between the EFM signal's zero crossings, 3..11
-channel bits, the input of an EFM decoder (F3 frames, CIRC, 44.1 kHz PCM; not part of this
-project) -- and <out>.efm.json, a summary with the one check that needs no code table: how
+channel bits, the input of efm_decode.py (F3 frames, CIRC, 44.1 kHz PCM; DESIGN.md section
+7d) -- and <out>.efm.json, a summary with the one check that needs no code table: how
 many consecutive sync patterns (11, 11) lie 588 channel bits apart.  The rule is this
 project's own (BUILD-DEFINED).  The sample range is widened outward to
 whole segments of 2^20 samples.  Loader selection by extension as lddecode.py.

@@ -12,7 +12,8 @@ and the same outputs: <outfile>.tbc (native uint16 frames) and <outfile>.pcm
 <outfile>.json (per-frame VBI and per-field metadata, one JSON list) and
 --comb (<outfile>.rgb: comb-ntsc's default rgb48 744x480 frames; --comb-3d:
 comb-ntsc -d 3 -F's).  The comb alone, on a .tbc stream: comb_ntsc.py.  --efm adds
-<outfile>.efm (the EFM digital-audio run lengths, as efm_extract.py writes them).
+<outfile>.efm (the EFM digital-audio run lengths, as efm_extract.py writes them), --efm-pcm
+also <outfile>.efm.pcm (their 44.1 kHz PCM, as efm_decode.py writes it).
 """
 import argparse
 import json
@@ -124,6 +125,13 @@ def parse(argv=None):
                    help='after the decode, write the EFM (digital audio) run lengths of the samples it consumed to '
                         '<outfile>.efm and a summary to <outfile>.efm.json (build-defined rule, DESIGN.md section 7c; '
                         'the same as efm_extract.py over that range); one process, no epochs, not with -c')
+    p.add_argument('--efm-pcm', action='store_true',
+                   help='implies --efm (and its conditions); then decode <outfile>.efm to 44.1 kHz stereo s16le in '
+                        '<outfile>.efm.pcm and a summary in <outfile>.efm.pcm.json (F3 frames, CIRC; build-defined rule, '
+                        'DESIGN.md section 7d; the same as efm_decode.py on that file)')
+    p.add_argument('--efm-table', default=None,
+                   help='the EFM code table for --efm-pcm: 256 lines of 14 channel bits, value 0 first '
+                        '(default: tests/golden/efm_map.txt of this repository)')
     p.add_argument('--no-json', action='store_true', help='do not write <outfile>.json')
     p.add_argument('--stats-json', default=None,
                    help='one process: write a timing breakdown of the run (read, decode, write) to this file')
@@ -155,6 +163,8 @@ def main(argv=None):
         return 1
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
+    if args.efm_pcm:
+        args.efm = True
     if args.efm and (world > 1 or args.epoch_frames or args.manifest or args.cut):
         print("ERROR: --efm is a second pass of one plain decode: not with sharding (WORLD_SIZE > 1), "
               "--epoch-frames / --manifest or -c; run efm_extract.py on the capture instead")
@@ -313,6 +323,13 @@ def main(argv=None):
         print('efm: %d run lengths from samples [%d, %d), %d of %d syncs 588 bits apart, %.2f s' % (
             summ['run_lengths'], summ['samples'][0], summ['samples'][1], summ['frames_588'],
             max(summ['syncs'] - 1, 0), time.perf_counter() - t1))
+    if args.efm_pcm:
+        from ldgpu import efmdec
+        t1 = time.perf_counter()
+        summ = efmdec.decode_file(dec.ctx, outname + '.efm', outname, table=args.efm_table)
+        print('efm-pcm: %d frames, %d samples (%d flagged values), Q: %d of %d sections good, %.2f s' % (
+            summ['frames'], summ['samples'], summ['flagged'], summ['q']['crc_good'], summ['q']['sections'],
+            time.perf_counter() - t1))
     return 0
 
 

@@ -3,8 +3,8 @@ DESIGN.md section 7c): walk a capture file in chunks of whole segments, each wit
 needs, concatenate the bytes, and summarise them.
 
 The output is one byte per run length (3..11 channel bits): what this project understands
-later ld-decode versions to write as <outfile>.efm, the input of an EFM decoder (F3 frames,
-CIRC, PCM), which this project does not have.
+later ld-decode versions to write as <outfile>.efm, the input of the EFM decode (F3 frames,
+CIRC, PCM: ldgpu/efmdec.py).
 """
 import numpy as np
 

@@ -32,7 +32,8 @@ EXPORTS = ['ldg_create', 'ldg_destroy', 'ldg_last_error', 'ldg_set_filters', 'ld
            'ldg_stream_close', 'ldg_device_memory',
            'ldg_dropout_defaults', 'ldg_set_dropout_opts', 'ldg_field_dropouts',
            'ldg_stack_frames', 'ldg_conceal_frames', 'ldg_stack_stats',
-           'ldg_efm_defaults', 'ldg_efm_set_opts', 'ldg_efm_window', 'ldg_efm_extract', 'ldg_efm_debug_read']
+           'ldg_efm_defaults', 'ldg_efm_set_opts', 'ldg_efm_window', 'ldg_efm_extract', 'ldg_efm_debug_read',
+           'ldg_efmdec_set_table', 'ldg_efmdec_reset', 'ldg_efmdec_feed', 'ldg_efmdec_read']
 STACK_MAX_SOURCES = 16            # LDG_STACK_MAX_SOURCES
 STACK_MODES = {'median': 0, 'mean': 1, 'smart-mean': 2}      # LDG_STACK_*
 STACK_STATS = ('h2d_s', 'kernel_s', 'd2h_s', 'calls')        # ldg_stack_stats, in order
@@ -111,6 +112,19 @@ class EfmSeg(C.Structure):
     _fields_ = [('emitted', C.c_int64), ('ignored', C.c_int64), ('clamped_low', C.c_int64),
                 ('clamped_high', C.c_int64), ('final_P', C.c_double)]
 
+
+class EfmdecInfo(C.Structure):
+    """ldg_efmdec_info: what one ldg_efmdec_feed added, and its counters."""
+    _fields_ = [(k, C.c_int64) for k in (
+        'first_frame', 'frames', 'first_sample', 'samples', 'candidates', 'confirmed', 'coasted', 'breaks',
+        'bad_symbols', 'c1_pass', 'c1_fixed', 'c1_erased', 'c2_pass', 'c2_fixed', 'c2_erasure_solved', 'c2_failed',
+        'c2_unsolved', 'flagged', 'averaged', 'muted', 'held_runs')]
+
+
+# ldg_efmdec_read: name -> (LDG_EFMDEC_*, dtype, values per sample or frame)
+EFMDEC_ARRAYS = {'pcm': (0, np.int16, 2), 'flags': (1, np.uint8, 2), 'subcode': (2, np.uint16, 1),
+                 'starts': (10, np.int64, 1), 'f3': (11, np.uint8, 32), 'c1': (12, np.uint8, 28),
+                 'c1_flags': (13, np.uint8, 1), 'c2': (14, np.uint8, 28), 'c2_flags': (15, np.uint32, 1)}
 
 EFM_SEG = 1 << 20                 # RF samples per EFM segment (csrc/efm_plan.hpp SEG)
 EFM_NTAPS = 255
@@ -247,6 +261,11 @@ def load(path=None):
                                     C.c_int64, C.POINTER(C.c_int64), vp]
     lib.ldg_efm_debug_read.argtypes = [vp, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64)]
     lib.ldg_efm_debug_read.restype = C.c_int64
+    lib.ldg_efmdec_set_table.argtypes = [vp, vp, C.c_int]
+    lib.ldg_efmdec_reset.argtypes = [vp]
+    lib.ldg_efmdec_feed.argtypes = [vp, vp, C.c_int64, C.c_int, C.POINTER(EfmdecInfo)]
+    lib.ldg_efmdec_read.argtypes = [vp, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64)]
+    lib.ldg_efmdec_read.restype = C.c_int64
     lib.ldg_version.restype = C.c_char_p
     lib.ldg_device_count.restype = C.c_int
     _lib = lib
@@ -769,6 +788,36 @@ class Context:
             a = np.zeros(a.size * 4, dtype=np.float64)
         a = a[:rc // 8].copy()
         return (int(first.value), a) if what == 'z' else a
+
+    # ---- EFM decode (build-defined; include/ldgpu.h) -------------
+    def efmdec_set_table(self, inverse):
+        """ldg_efmdec_set_table: the 16384-entry inverse code table (uint16); resets the stream."""
+        t = np.ascontiguousarray(inverse, dtype=np.uint16)
+        self._check(self.lib.ldg_efmdec_set_table(self.h, t.ctypes.data, t.size), 'ldg_efmdec_set_table')
+
+    def efmdec_reset(self):
+        self._check(self.lib.ldg_efmdec_reset(self.h), 'ldg_efmdec_reset')
+
+    def efmdec_feed(self, rl, final=False):
+        """ldg_efmdec_feed: the next run lengths (uint8 array) -> ldg_efmdec_info as a dict."""
+        buf = np.ascontiguousarray(rl, dtype=np.uint8)
+        info = EfmdecInfo()
+        self._check(self.lib.ldg_efmdec_feed(self.h, buf.ctypes.data, buf.size, int(bool(final)), C.byref(info)),
+                    'ldg_efmdec_feed')
+        return {k: getattr(info, k) for k, _ in EfmdecInfo._fields_}
+
+    def efmdec_read(self, what, count):
+        """ldg_efmdec_read of the last efmdec_feed: EFMDEC_ARRAYS[what] for `count` samples
+        (pcm, flags) or frames (the others) -> (index of the first, array)."""
+        w, dt, per = EFMDEC_ARRAYS[what]
+        a = np.zeros((int(count), per) if per > 1 else int(count), dtype=dt)
+        first = C.c_int64(0)
+        if a.size == 0:
+            return 0, a
+        rc = self.lib.ldg_efmdec_read(self.h, w, a.ctypes.data, a.nbytes, C.byref(first))
+        if rc != a.nbytes:
+            raise LDGError('ldg_efmdec_read(%s) -> %d, expected %d bytes' % (what, rc, a.nbytes))
+        return int(first.value), a
 
     # ---- profiling / tooling -------------------------------------------------------
     def profile(self, on=True):
