@@ -466,6 +466,14 @@ int64_t ldg_efmdec_read(ldg_ctx* ctx, int what, void* dst, int64_t cap, int64_t*
  *       weight map that flow gave [float64, 252 x 840].  They ignore `slot`, synchronise the
  *       device, and return LDG_EINVAL until a frame has taken the flow path since the context's
  *       creation or the last ldg_comb_reset (70..73: the comb's second frame; 74, 75: its third).
+ *       80..84: the PAL Y/C decoder's buffers as its last launch left them, for that launch's m
+ *       frames (ldg_comb_pal takes n frames in chunks of max_frames: m is the last chunk's):
+ *       80 SplitIQ's signed chroma of lines 24..624, 0 outside columns [4, 1131) [float64,
+ *       m x 601 x 1136]; 81 the burst angle per line, degrees in [0, 360) [float64, m x 625];
+ *       82 the V-switch phase of each frame [int32, m]; 83 the burst-level EMA that line 44 + j
+ *       used [float64, m x 579]; 84 the EMA carried into the next call, -1 after a reset
+ *       [float64, 1].  They ignore `slot`, synchronise the device, and return LDG_EINVAL until
+ *       the context has run the PAL decoder.
  * Copies up to `cap` bytes to host `dst`; returns bytes copied (>= 0) or an error. */
 int64_t ldg_debug_read(ldg_ctx* ctx, int slot, int what, void* dst, int64_t cap);
 

@@ -269,6 +269,7 @@ struct ldg_ctx {
   double *pal_cv = nullptr, *pal_angle = nullptr, *pal_abl = nullptr, *pal_state = nullptr;
   int32_t* pal_phase = nullptr;
   int pal_scur = 0;                 // pal_state[pal_scur]: the burst-level EMA entering the next call
+  int pal_last_m = 0;               // frames of the last pal_launch (debug reads 80..84; 0: none yet)
   int comb3_hist = 0;               // 3D: input frames held in the window (0..2)
   // 3D with optical flow (flow.hip): field luma, pyramid, expansions, flows, weight maps
   struct FlowState {
@@ -2586,6 +2587,7 @@ static int pal_launch(ldg_ctx* ctx, hipStream_t s, const uint16_t* src, int m) {
   ctx->pal_scur = cur ^ 1;
   LDG_LAUNCH_ON(s, "pal_out", ldg_k_pal_out, m * pal::OUT_H, 256, src, ctx->pal_cv, ctx->pal_angle,
                 ctx->pal_phase, ctx->pal_abl, ctx->pal_rgb);
+  ctx->pal_last_m = m;
   return check_launch(ctx, "pal comb kernels");
 }
 
@@ -2644,6 +2646,34 @@ int64_t ldg_debug_read(ldg_ctx* ctx, int slot, int what, void* dst, int64_t cap)
     } else {
       src = F.kmap + (int64_t)F.klast * px;
       bytes = px * 8;
+    }
+    if (bytes > cap) bytes = cap;
+    if (hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) != hipSuccess) return LDG_EDEVICE;
+    return bytes;
+  }
+  if (ctx && dst && what >= 80 && what <= 84) {
+    // the PAL Y/C decoder's buffers for the m frames of the last pal_launch: 80 SplitIQ's signed chroma,
+    // 81 the burst angles, 82 the V-switch phases, 83 the burst-level EMA per line; 84 the carried EMA state
+    const int64_t m = ctx->pal_last_m;
+    if (!ctx->pal_state || m <= 0) return LDG_EINVAL;
+    if (hipSetDevice(ctx->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return LDG_EDEVICE;
+    const void* src = nullptr;
+    int64_t bytes = 0;
+    if (what == 80) {
+      src = ctx->pal_cv;
+      bytes = m * pal::CV_ROWS * pal::CV_STRIDE * 8;
+    } else if (what == 81) {
+      src = ctx->pal_angle;
+      bytes = m * pal::IN_Y * 8;
+    } else if (what == 82) {
+      src = ctx->pal_phase;
+      bytes = m * 4;
+    } else if (what == 83) {
+      src = ctx->pal_abl;
+      bytes = m * pal::ABL_LINES * 8;
+    } else {
+      src = ctx->pal_state + ctx->pal_scur;
+      bytes = 8;
     }
     if (bytes > cap) bytes = cap;
     if (hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) != hipSuccess) return LDG_EDEVICE;

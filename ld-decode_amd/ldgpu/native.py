@@ -589,6 +589,19 @@ class Context:
                                           out.ctypes.data_as(C.c_void_p)), 'ldg_comb_pal')
         return out
 
+    def comb_pal_stages(self):
+        """The PAL Y/C decoder's buffers as its last launch left them (ldg_debug_read 80..84), for
+        that launch's m frames (the last chunk of at most max_frames of a longer call): cv
+        [m, 601, 1136] SplitIQ's signed chroma of lines 24..624, angle [m, 625] the burst angles
+        (degrees), phase [m] the V-switch votes, abl [m, 579] the burst-level EMA line 44 + j
+        used, state the EMA carried into the next call.  LDGError before any PAL call."""
+        phase = self.debug(0, 82, np.int32, self.max_frames)
+        m = phase.size
+        return dict(cv=self.debug(0, 80, np.float64, m * 601 * 1136).reshape(m, 601, 1136),
+                    angle=self.debug(0, 81, np.float64, m * 625).reshape(m, 625), phase=phase,
+                    abl=self.debug(0, 83, np.float64, m * 579).reshape(m, 579),
+                    state=float(self.debug(0, 84, np.float64, 1)[0]))
+
     def comb_ntsc_device(self, n):
         """Comb the first n frames of the context's device frame buffer (ldg_assemble_frames
         with out=NULL) into the context's device rgb buffer (benchmark mode)."""

@@ -181,9 +181,19 @@ LIB_PAL = os.path.join(HERE, '_build', 'libcombpal.so')
 
 
 class CombPAL:
-    """The build-defined PAL Y/C decoder's checker (oracle/combpal.cpp): one process."""
+    """The build-defined PAL Y/C decoder's checker (oracle/combpal.cpp): one process.
+    rotate: ToRGB's chroma rotation evaluated as the GPU kernel does (one sin / cos per row and
+    a 2 x 2 rotation) in place of the reference's mag * cis(atan2 + adj); the default is the
+    reference's form.  process(frames, keep_stages=True) appends one dict per frame to
+    `stages`: cv [601, 1136] SplitIQ's signed chroma of lines 24..624 before the U / V hold,
+    angle [625] the burst angles (degrees), bsum [625, 2] the burst window's sums (i, q) they
+    were taken of, phase / phasecount the V-switch vote, abl [579] the burst-level EMA line
+    44 + j used, and COUNTERS' branch counts."""
 
-    def __init__(self):
+    COUNTERS = ('ynr_clamp', 'kn_gt_3kp', 'kp_gt_3kn', 'both_zero', 'both_zero_similar', 'level0',
+                'rgb_lo', 'rgb_hi')
+
+    def __init__(self, rotate=False):
         if not os.path.exists(LIB_PAL) or os.path.getmtime(LIB_PAL) < os.path.getmtime(os.path.join(HERE, 'combpal.cpp')):
             subprocess.check_call(['make', '-s', '-C', HERE])
         self.lib = C.CDLL(LIB_PAL)
@@ -192,17 +202,37 @@ class CombPAL:
         self.lib.combpal_process.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         self.lib.combpal_aburstlev.argtypes = [C.c_void_p]
         self.lib.combpal_aburstlev.restype = C.c_double
+        self.lib.combpal_set_rotate.argtypes = [C.c_void_p, C.c_int]
+        self.lib.combpal_stages.argtypes = [C.c_void_p] * 7
         self.h = self.lib.combpal_create()
+        self.lib.combpal_set_rotate(self.h, int(bool(rotate)))
+        self.stages = []
 
     def __del__(self):
         if getattr(self, 'h', None):
             self.lib.combpal_destroy(self.h)
             self.h = None
 
-    def process(self, frames):
+    def _read_stages(self):
+        cv = np.zeros((PAL_IN_Y - 24, 1136), dtype=np.float64)
+        angle = np.zeros(PAL_IN_Y, dtype=np.float64)
+        bsum = np.zeros((PAL_IN_Y, 2), dtype=np.float64)
+        vote = np.zeros(2, dtype=np.int32)
+        abl = np.zeros(579, dtype=np.float64)
+        n = np.zeros(len(self.COUNTERS), dtype=np.int64)
+        self.lib.combpal_stages(self.h, *(a.ctypes.data for a in (cv, angle, bsum, vote, abl, n)))
+        return dict(cv=cv, angle=angle, bsum=bsum, phase=int(vote[0]), phasecount=int(vote[1]), abl=abl,
+                    counters=dict(zip(self.COUNTERS, (int(v) for v in n))))
+
+    def process(self, frames, keep_stages=False):
         f = np.ascontiguousarray(frames, dtype=np.uint16).reshape(-1, PAL_IN_Y, PAL_IN_X)
         out = np.zeros((f.shape[0], PAL_OUT_H, PAL_OUT_W, 3), dtype=np.uint16)
-        self.lib.combpal_process(self.h, f.shape[0], f.ctypes.data, out.ctypes.data)
+        if not keep_stages:
+            self.lib.combpal_process(self.h, f.shape[0], f.ctypes.data, out.ctypes.data)
+            return out
+        for k in range(f.shape[0]):
+            self.lib.combpal_process(self.h, 1, f[k].ctypes.data, out[k].ctypes.data)
+            self.stages.append(self._read_stages())
         return out
 
     @property
