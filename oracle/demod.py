@@ -117,6 +117,13 @@ class RFDemod(FilterSet):
 
     def demod(self, capture, start, length, mtf_level=0):
         """lddecode_core.py:373-427.  Returns (video, audio) or None on loader failure."""
+        st = self.demod_stages(capture, start, length, mtf_level)
+        return None if st is None else (st[0], st[2])
+
+    def demod_stages(self, capture, start, length, mtf_level=0):
+        """demod() with its intermediate kept: (video, audio1, audio2), audio1 the 2.5 MHz
+        audio assembled from the blocks (what audio_phase2 is given), audio2 what demod()
+        returns; both None without analog audio.  None on loader failure."""
         start0, end, starts = self.block_starts(start, length)
         step = self.blocklen - self.blockcut - self.blockcut_end
         n_out = end - start0 + 1
@@ -150,5 +157,5 @@ class RFDemod(FilterSet):
                     a0, a1 = off // ds, (off + copylen) // ds
                     audio[k][a0:a1] = ta[k][self.blockcut // ds:(self.blockcut + copylen) // ds]
         if ta is not None:
-            return video, self.audio_phase2(audio)
-        return video, None
+            return video, audio, self.audio_phase2(audio)
+        return video, None, None

@@ -48,8 +48,10 @@ def scale(buf, begin, end, tgtlen):
     return interpolate.splev(xo, spl)[:-1]
 
 
-def downscale_audio(audio, lineinfo, rf, linecount, timeoffset=0, freq=48000.0, scale_=64):
-    """lddecode_core.py:431-484: 48 kHz stereo from the 625 kHz field audio."""
+def downscale_audio(audio, lineinfo, rf, linecount, timeoffset=0, freq=48000.0, scale_=64, unrounded=False):
+    """lddecode_core.py:431-484: 48 kHz stereo from the 625 kHz field audio.
+    unrounded: also return, per output sample, the value that is rounded and clipped
+    (float64, interleaved like the PCM), for tests of the rounding."""
     sp = rf.SysParams
     frametime = (sp['line_period'] * linecount) / 1000000
     gap = 1 / freq
@@ -69,6 +71,7 @@ def downscale_audio(audio, lineinfo, rf, linecount, timeoffset=0, freq=48000.0, 
         locs[i] = pos / scale_
     out = np.zeros((2 * (len(ticks) - 1)), dtype=np.int32)
     out16 = np.zeros((2 * (len(ticks) - 1)), dtype=np.int16)
+    raw = np.zeros((2 * (len(ticks) - 1)), dtype=np.float64)
     for i in range(len(ticks) - 1):
         left = audio['audio_left'][int(locs[i])]
         right = audio['audio_right'][int(locs[i])]
@@ -76,9 +79,13 @@ def downscale_audio(audio, lineinfo, rf, linecount, timeoffset=0, freq=48000.0, 
         right *= swow[i]
         left -= sp['audio_lfreq']
         right -= sp['audio_rfreq']
-        out[(i * 2) + 0] = int(np.round(left * 32767 / 150000))
-        out[(i * 2) + 1] = int(np.round(right * 32767 / 150000))
+        raw[(i * 2) + 0] = left * 32767 / 150000
+        raw[(i * 2) + 1] = right * 32767 / 150000
+        out[(i * 2) + 0] = int(np.round(raw[(i * 2) + 0]))
+        out[(i * 2) + 1] = int(np.round(raw[(i * 2) + 1]))
     np.clip(out, -32766, 32766, out=out16)
+    if unrounded:
+        return out16, ticks[-1] - frametime, raw
     return out16, ticks[-1] - frametime
 
 
