@@ -449,6 +449,56 @@ int ldg_efmdec_feed(ldg_ctx* ctx, const uint8_t* rl, int64_t n, int final, ldg_e
 #define LDG_EFMDEC_C2_FLAGS 15
 int64_t ldg_efmdec_read(ldg_ctx* ctx, int what, void* dst, int64_t cap, int64_t* first);
 
+/* ---- EFM data sectors (BUILD-DEFINED: the reference snapshot has no sector decoder; the layout
+ * is CD-ROM mode 1 of ECMA-130) ----
+ * The bytes of the decoded EFM stream before concealment, each with an erasure flag (its own C2
+ * flag), to 2352-byte sectors: a grid from the sync pattern 00 FF x 10 00 confirmed at +-2352
+ * bytes (coasting over at most 75 sectors), descrambling, the EDC (CRC-32, 0xD8018001 reflected)
+ * and rounds of the Reed-Solomon product code's P and Q words (one error, or up to two erasures a
+ * word) until the EDC verifies.  An unverified repair is never passed on.  All integers.  The
+ * stream is fed in calls of any size; the result does not depend on how it is cut. */
+typedef struct ldg_efmsec_info { /* one call of the stage; counters are this call's share */
+  int64_t first_byte, bytes;     /* the bytes this call added, indexed from the stream's first */
+  int64_t first_sector, sectors; /* the sectors it emitted, in grid order                       */
+  int64_t candidates, confirmed; /* sync patterns; those with another at +-2352                 */
+  int64_t coasted, breaks;       /* sectors started without a confirmed sync of their own; gaps > 75 sectors */
+  int64_t good, corrected, bad, other; /* sectors by status                                     */
+  int64_t p_fixed, q_fixed;      /* P and Q words changed, over all rounds                      */
+  int64_t erased_bytes;          /* flagged bytes 12..2351 of the sectors emitted               */
+  int64_t held_bytes;            /* bytes kept for the next call                                */
+} ldg_efmsec_info;
+#define LDG_EFMSEC_GOOD 0      /* no flag on bytes 12..2067, mode 1, EDC matches: untouched     */
+#define LDG_EFMSEC_CORRECTED 1 /* verified after `rounds` rounds of P and Q                     */
+#define LDG_EFMSEC_BAD 2       /* not verified: the descrambled bytes without any repair        */
+#define LDG_EFMSEC_OTHER 3     /* as BAD, but an unflagged header whose mode byte is not 1      */
+typedef struct ldg_efmsec_rec {  /* one sector */
+  int32_t status, rounds, erased; /* LDG_EFMSEC_*; rounds run; flagged bytes 12..2351           */
+  uint8_t minute, second, frame, mode; /* bytes 12..15 as stored                                */
+} ldg_efmsec_rec;
+/* on != 0: from now on every ldg_efmdec_feed hands the stage the frames whose samples it emits,
+ * on the device (ldg_efmsec_last_info and ldg_efmsec_read then describe that call); 0: detached.
+ * Allocates the stage's state and resets its stream; ldg_efmdec_reset resets it too. */
+int ldg_efmsec_enable(ldg_ctx* ctx, int on);
+/* Forgets the stream: the next bytes are the stream's first. */
+int ldg_efmsec_reset(ldg_ctx* ctx);
+/* The stage on its own: the next n bytes and their erasure flags (host memory; non-zero: erased).
+ * final != 0 ends the stream.  Synchronous, on a stream of its own; its kernels report through
+ * ldg_profile_read as efmsec_*.  After an error the stream is undefined until ldg_efmsec_reset. */
+int ldg_efmsec_feed(ldg_ctx* ctx, const uint8_t* bytes, const uint8_t* erased, int64_t n, int final, ldg_efmsec_info* info);
+/* The info of the stage's last call (ldg_efmsec_feed, or ldg_efmdec_feed with the stage enabled). */
+int ldg_efmsec_last_info(ldg_ctx* ctx, ldg_efmsec_info* info);
+/* What the stage's last call produced: DATA [uint8, 2048 per sector: bytes 16..2063], SECTORS
+ * [uint8, 2352 per sector, descrambled], RECORDS [ldg_efmsec_rec per sector], STARTS [int64 per
+ * sector: its first byte's index], and for parity the bytes the call added: BYTES, ERASED [uint8
+ * each].  Copies up to cap bytes to dst; returns the bytes copied or an error. */
+#define LDG_EFMSEC_DATA 0
+#define LDG_EFMSEC_SECTORS 1
+#define LDG_EFMSEC_RECORDS 2
+#define LDG_EFMSEC_STARTS 3
+#define LDG_EFMSEC_BYTES 10
+#define LDG_EFMSEC_ERASED 11
+int64_t ldg_efmsec_read(ldg_ctx* ctx, int what, void* dst, int64_t cap);
+
 /* Debug / parity access to the per-read device arrays of a live slot.
  * what: 0..4 demod channels (demod, demod_05, demod_sync, demod_burst, demod_pilot)
  *       [float64, n_out] (demod_05, demod_sync and demod_burst are expanded on request from

@@ -1,6 +1,11 @@
 // Host side of the EFM decode (efmdec.hip; build-defined, DESIGN.md section 7d):
 // ldg_efmdec_* of include/ldgpu.h.  Unity-built after efm.inc (efm_grow is its).
 
+// efmsec.inc: the data-sector stage, fed each call's frames on the device when it is enabled
+static bool efmsec_enabled(ldg_ctx* ctx);
+static void efmsec_restart(ldg_ctx* ctx);
+static int efmsec_take(ldg_ctx* ctx, const uint8_t* c2, const uint32_t* c2f, int64_t first, int64_t nbytes, bool fin);
+
 struct ldg_efmdec_state {
   bool have_table = false;
   hipStream_t st = nullptr;
@@ -126,6 +131,7 @@ int ldg_efmdec_reset(ldg_ctx* ctx) {
   D->tail.clear();
   D->ended = false;
   D->last_held = D->last_fresh = D->last_first_frame = D->last_elems = D->last_first_sample = 0;
+  efmsec_restart(ctx);
   return LDG_OK;
 }
 
@@ -286,6 +292,9 @@ int ldg_efmdec_feed(ldg_ctx* ctx, const uint8_t* rl, int64_t n, int final_, ldg_
   D->last_first_frame = info->first_frame;
   D->last_elems = elems;
   D->last_first_sample = info->first_sample;
+  // the same frames' bytes, before concealment, to the sector stage (24 a frame: two a value)
+  if (efmsec_enabled(ctx))
+    if (int rc = efmsec_take(ctx, D->d_c2, D->d_c2f, D->circ.e0 - D->circ.g0, elems * 2, fin)) return rc;
   circ_advance(&D->circ, P);
   D->tail.erase(D->tail.begin(), D->tail.begin() + (size_t)g.tail_idx);
   info->held_runs = (int64_t)D->tail.size();

@@ -13,7 +13,8 @@ and the same outputs: <outfile>.tbc (native uint16 frames) and <outfile>.pcm
 --comb (<outfile>.rgb: comb-ntsc's default rgb48 744x480 frames; --comb-3d:
 comb-ntsc -d 3 -F's).  The comb alone, on a .tbc stream: comb_ntsc.py.  --efm adds
 <outfile>.efm (the EFM digital-audio run lengths, as efm_extract.py writes them), --efm-pcm
-also <outfile>.efm.pcm (their 44.1 kHz PCM, as efm_decode.py writes it).
+also <outfile>.efm.pcm (their 44.1 kHz PCM, as efm_decode.py writes it), --efm-data also
+<outfile>.efm.data (the CD-ROM mode 1 sectors' user bytes, as efm_decode.py --data writes them).
 """
 import argparse
 import json
@@ -129,6 +130,10 @@ def parse(argv=None):
                    help='implies --efm (and its conditions); then decode <outfile>.efm to 44.1 kHz stereo s16le in '
                         '<outfile>.efm.pcm and a summary in <outfile>.efm.pcm.json (F3 frames, CIRC; build-defined rule, '
                         'DESIGN.md section 7d; the same as efm_decode.py on that file)')
+    p.add_argument('--efm-data', action='store_true',
+                   help='implies --efm-pcm; also decode the CD-ROM mode 1 sectors the channel carries to <outfile>.efm.data '
+                        '(2048 bytes a sector) and a summary in <outfile>.efm.data.json (descramble, EDC, Reed-Solomon '
+                        'product code; build-defined rule, DESIGN.md section 7e; the same as efm_decode.py --data)')
     p.add_argument('--efm-table', default=None,
                    help='the EFM code table for --efm-pcm: 256 lines of 14 channel bits, value 0 first '
                         '(default: tests/golden/efm_map.txt of this repository)')
@@ -163,6 +168,8 @@ def main(argv=None):
         return 1
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
+    if args.efm_data:
+        args.efm_pcm = True
     if args.efm_pcm:
         args.efm = True
     if args.efm and (world > 1 or args.epoch_frames or args.manifest or args.cut):
@@ -326,10 +333,18 @@ def main(argv=None):
     if args.efm_pcm:
         from ldgpu import efmdec
         t1 = time.perf_counter()
-        summ = efmdec.decode_file(dec.ctx, outname + '.efm', outname, table=args.efm_table)
+        dsumm = None
+        if args.efm_data:
+            from ldgpu import efmsec
+            summ, dsumm = efmsec.decode_file(dec.ctx, outname + '.efm', outname, table=args.efm_table)
+        else:
+            summ = efmdec.decode_file(dec.ctx, outname + '.efm', outname, table=args.efm_table)
         print('efm-pcm: %d frames, %d samples (%d flagged values), Q: %d of %d sections good, %.2f s' % (
             summ['frames'], summ['samples'], summ['flagged'], summ['q']['crc_good'], summ['q']['sections'],
             time.perf_counter() - t1))
+        if dsumm is not None:
+            print('efm-data: %d sectors (%d good, %d corrected, %d bad, %d other), %d coasted' % (
+                dsumm['sectors'], dsumm['good'], dsumm['corrected'], dsumm['bad'], dsumm['other'], dsumm['coasted']))
     return 0
 
 

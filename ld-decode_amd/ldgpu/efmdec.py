@@ -41,10 +41,11 @@ def inverse_table(table):
     return inv
 
 
-def decode(ctx, rl, chunk_bytes=None, table=None, keep=False):
+def decode(ctx, rl, chunk_bytes=None, table=None, keep=False, after_feed=None):
     """The run lengths `rl` (uint8 array, e.g. a np.memmap) -> dict with pcm int16[n, 2], flags
     uint8[n, 2], subcode uint16[frames] and the counters; keep: also the parity arrays.
-    ctx: a native.Context.  The result does not depend on chunk_bytes."""
+    ctx: a native.Context.  The result does not depend on chunk_bytes.  after_feed: called after
+    every feed (ldgpu.efmsec collects the sector stage's output there)."""
     ctx.efmdec_set_table(inverse_table(load_table(table)))
     n = int(rl.size)
     step = n if not chunk_bytes else max(int(chunk_bytes), 1)
@@ -58,6 +59,8 @@ def decode(ctx, rl, chunk_bytes=None, table=None, keep=False):
             tot[k] += info[k]
         for k in parts:
             parts[k].append(ctx.efmdec_read(k, info['samples'] if k in ('pcm', 'flags') else info['frames'])[1])
+        if after_feed is not None:
+            after_feed()
         at = b
         if at >= n:
             break
@@ -98,16 +101,17 @@ def q_decode(sub):
             'last_time': times[-1] if times else None}
 
 
-def decode_file(ctx, path, outbase, chunk_bytes=1 << 24, table=None, stats=False):
+def decode_file(ctx, path, outbase, chunk_bytes=1 << 24, table=None, stats=False, after_feed=None, all_kernels=None):
     """`path`'s run lengths into <outbase>.efm.pcm (s16le stereo, 44.1 kHz) and
-    <outbase>.efm.pcm.json; returns the summary."""
+    <outbase>.efm.pcm.json; returns the summary.  all_kernels: a dict that receives every kernel's
+    time with stats (ldgpu.efmsec reads its own from it)."""
     import json
     import time
     rl = np.memmap(path, dtype=np.uint8, mode='r') if os.path.getsize(path) else np.zeros(0, dtype=np.uint8)
     if stats:
         ctx.profile(True)
     t0 = time.perf_counter()
-    res = decode(ctx, rl, chunk_bytes, table)
+    res = decode(ctx, rl, chunk_bytes, table, after_feed=after_feed)
     wall = time.perf_counter() - t0
     with open(outbase + '.efm.pcm', 'wb') as fh:
         fh.write(res['pcm'].astype('<i2').tobytes())
@@ -118,6 +122,8 @@ def decode_file(ctx, path, outbase, chunk_bytes=1 << 24, table=None, stats=False
     if stats:
         summ['wall_s'] = round(wall, 4)
         summ['kernels_ms'] = {k: round(v[1], 3) for k, v in ctx.profile_stats().items() if k.startswith('efmdec_')}
+        if all_kernels is not None:
+            all_kernels.update({k: round(v[1], 3) for k, v in ctx.profile_stats().items()})
         ctx.profile(False)
     with open(outbase + '.efm.pcm.json', 'w') as fh:
         json.dump(summ, fh, indent=1)

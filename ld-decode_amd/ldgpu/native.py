@@ -33,7 +33,8 @@ EXPORTS = ['ldg_create', 'ldg_destroy', 'ldg_last_error', 'ldg_set_filters', 'ld
            'ldg_dropout_defaults', 'ldg_set_dropout_opts', 'ldg_field_dropouts',
            'ldg_stack_frames', 'ldg_conceal_frames', 'ldg_stack_stats',
            'ldg_efm_defaults', 'ldg_efm_set_opts', 'ldg_efm_window', 'ldg_efm_extract', 'ldg_efm_debug_read',
-           'ldg_efmdec_set_table', 'ldg_efmdec_reset', 'ldg_efmdec_feed', 'ldg_efmdec_read']
+           'ldg_efmdec_set_table', 'ldg_efmdec_reset', 'ldg_efmdec_feed', 'ldg_efmdec_read',
+           'ldg_efmsec_enable', 'ldg_efmsec_reset', 'ldg_efmsec_feed', 'ldg_efmsec_last_info', 'ldg_efmsec_read']
 STACK_MAX_SOURCES = 16            # LDG_STACK_MAX_SOURCES
 STACK_MODES = {'median': 0, 'mean': 1, 'smart-mean': 2}      # LDG_STACK_*
 STACK_STATS = ('h2d_s', 'kernel_s', 'd2h_s', 'calls')        # ldg_stack_stats, in order
@@ -125,6 +126,20 @@ class EfmdecInfo(C.Structure):
 EFMDEC_ARRAYS = {'pcm': (0, np.int16, 2), 'flags': (1, np.uint8, 2), 'subcode': (2, np.uint16, 1),
                  'starts': (10, np.int64, 1), 'f3': (11, np.uint8, 32), 'c1': (12, np.uint8, 28),
                  'c1_flags': (13, np.uint8, 1), 'c2': (14, np.uint8, 28), 'c2_flags': (15, np.uint32, 1)}
+
+class EfmsecInfo(C.Structure):
+    """ldg_efmsec_info: what one call of the data-sector stage added, and its counters."""
+    _fields_ = [(k, C.c_int64) for k in (
+        'first_byte', 'bytes', 'first_sector', 'sectors', 'candidates', 'confirmed', 'coasted', 'breaks', 'good',
+        'corrected', 'bad', 'other', 'p_fixed', 'q_fixed', 'erased_bytes', 'held_bytes')]
+
+
+# ldg_efmsec_rec: a sector's status (LDG_EFMSEC_*), rounds, erased bytes and header as stored
+EFMSEC_REC = np.dtype([('status', '<i4'), ('rounds', '<i4'), ('erased', '<i4'), ('minute', 'u1'), ('second', 'u1'),
+                       ('frame', 'u1'), ('mode', 'u1')])
+# ldg_efmsec_read: name -> (LDG_EFMSEC_*, dtype, values per sector or byte)
+EFMSEC_ARRAYS = {'data': (0, np.uint8, 2048), 'sectors': (1, np.uint8, 2352), 'records': (2, EFMSEC_REC, 1),
+                 'starts': (3, np.int64, 1), 'bytes': (10, np.uint8, 1), 'erased': (11, np.uint8, 1)}
 
 EFM_SEG = 1 << 20                 # RF samples per EFM segment (csrc/efm_plan.hpp SEG)
 EFM_NTAPS = 255
@@ -266,6 +281,12 @@ def load(path=None):
     lib.ldg_efmdec_feed.argtypes = [vp, vp, C.c_int64, C.c_int, C.POINTER(EfmdecInfo)]
     lib.ldg_efmdec_read.argtypes = [vp, C.c_int, vp, C.c_int64, C.POINTER(C.c_int64)]
     lib.ldg_efmdec_read.restype = C.c_int64
+    lib.ldg_efmsec_enable.argtypes = [vp, C.c_int]
+    lib.ldg_efmsec_reset.argtypes = [vp]
+    lib.ldg_efmsec_feed.argtypes = [vp, vp, vp, C.c_int64, C.c_int, C.POINTER(EfmsecInfo)]
+    lib.ldg_efmsec_last_info.argtypes = [vp, C.POINTER(EfmsecInfo)]
+    lib.ldg_efmsec_read.argtypes = [vp, C.c_int, vp, C.c_int64]
+    lib.ldg_efmsec_read.restype = C.c_int64
     lib.ldg_version.restype = C.c_char_p
     lib.ldg_device_count.restype = C.c_int
     _lib = lib
@@ -831,6 +852,43 @@ class Context:
         if rc != a.nbytes:
             raise LDGError('ldg_efmdec_read(%s) -> %d, expected %d bytes' % (what, rc, a.nbytes))
         return int(first.value), a
+
+    # ---- EFM data sectors (build-defined; include/ldgpu.h) -------
+    def efmsec_enable(self, on=True):
+        """ldg_efmsec_enable: efmdec_feed hands its frames to the sector stage (or no longer)."""
+        self._check(self.lib.ldg_efmsec_enable(self.h, int(bool(on))), 'ldg_efmsec_enable')
+
+    def efmsec_reset(self):
+        self._check(self.lib.ldg_efmsec_reset(self.h), 'ldg_efmsec_reset')
+
+    def efmsec_feed(self, data, erased, final=False):
+        """ldg_efmsec_feed: the next bytes and their erasure flags (uint8 arrays of one size) ->
+        ldg_efmsec_info as a dict."""
+        by = np.ascontiguousarray(data, dtype=np.uint8)
+        er = np.ascontiguousarray(erased, dtype=np.uint8)
+        if by.shape != er.shape or by.ndim != 1:
+            raise ValueError('efmsec_feed: bytes and flags are flat arrays of one size')
+        info = EfmsecInfo()
+        self._check(self.lib.ldg_efmsec_feed(self.h, by.ctypes.data, er.ctypes.data, by.size, int(bool(final)),
+                                             C.byref(info)), 'ldg_efmsec_feed')
+        return {k: getattr(info, k) for k, _ in EfmsecInfo._fields_}
+
+    def efmsec_last_info(self):
+        info = EfmsecInfo()
+        self._check(self.lib.ldg_efmsec_last_info(self.h, C.byref(info)), 'ldg_efmsec_last_info')
+        return {k: getattr(info, k) for k, _ in EfmsecInfo._fields_}
+
+    def efmsec_read(self, what, count):
+        """ldg_efmsec_read of the stage's last call: EFMSEC_ARRAYS[what] for `count` sectors
+        (bytes, erased: bytes)."""
+        w, dt, per = EFMSEC_ARRAYS[what]
+        a = np.zeros((int(count), per) if per > 1 else int(count), dtype=dt)
+        if a.size == 0:
+            return a
+        rc = self.lib.ldg_efmsec_read(self.h, w, a.ctypes.data, a.nbytes)
+        if rc != a.nbytes:
+            raise LDGError('ldg_efmsec_read(%s) -> %d, expected %d bytes' % (what, rc, a.nbytes))
+        return a
 
     # ---- profiling / tooling -------------------------------------------------------
     def profile(self, on=True):
