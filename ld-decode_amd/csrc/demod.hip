@@ -16,6 +16,7 @@
 // recurrences in the time domain (iir.hpp); sync and burst are stored compact,
 // as per-chunk states the field kernels expand (chan.hpp).
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "common.hpp"
 #include "fft8k.hpp"
 #include "iir.hpp"
@@ -143,9 +144,6 @@ constexpr bool kProbeNoStore = true;
 constexpr bool kProbeNoStore = false;
 #endif
 
-// Store the pair of samples 2m, 2m+1 of a channel (o indexed by block position)
-// if kept ([BLOCKCUT, BLOCKCUT + copylen)); the wave-uniform test keeps the
-// common case (a wave's 64 pairs all kept or all dropped) branch-free.
 // A channel's 16-byte store, non-temporal ("nt": streamed, the lines still land
 // in L2 for the field kernels; -1.9% demod time against plain stores in an
 // interleaved A/B, "sc1" +13%).  Through the compiler's builtin, not inline asm:
@@ -167,18 +165,46 @@ __device__ __forceinline__ void st_park(double2* a, double2 z) { *a = z; }
 __device__ __forceinline__ unsigned long long* park_owner(double2* ospill) {
   return reinterpret_cast<unsigned long long*>(ospill + (int64_t)PARK_TOTAL * M);
 }
-__device__ __forceinline__ void store_pair(double* o, int m, double2 z, int copylen) {
-  const int p = 2 * m;
-  const int pw0 = 2 * (m & ~63);
-  if (pw0 >= BLOCKCUT && pw0 + 127 < BLOCKCUT + copylen) {
-    st_pair(o + p, z);
-  } else if (pw0 + 127 >= BLOCKCUT && pw0 < BLOCKCUT + copylen) {
+// Wave-uniform values and 32-bit lane offsets.  The channel bases,
+// the keep / drop decision of a wave's 64 pairs and the compact channels' bases are the same
+// for every lane of a wave; held in SGPRs they cost scalar compares and branches and the
+// stores take a scalar base plus one 32-bit lane offset, not a 64-bit vector add each.
+__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+// &base[i] for a wave-uniform base and 0 <= i * sizeof(T) < 2^32
+template <class T> __device__ __forceinline__ T* at32(T* base, int i) {
+  using B = std::conditional_t<std::is_const<T>::value, const char, char>;
+  return reinterpret_cast<T*>(reinterpret_cast<B*>(base) + (uint32_t)i * (uint32_t)sizeof(T));
+}
+
+// Store one wave's 64 pairs of a channel, block positions [lo, lo + 128), of which
+// [BLOCKCUT, BLOCKCUT + copylen) are kept.  ob: the byte address the wave's first pair of
+// q = 0 would take with lane offset 0 (wave-uniform); voff: this lane's byte offset; lo:
+// wave-uniform; l2 = 2 * lane.  All kept: one streaming 16-byte store per lane; all dropped:
+// nothing; only a wave that straddles an end of the kept range decides per lane.
+__device__ __forceinline__ void store_wave(char* ob, uint32_t voff, int lo, int l2, double2 z, int copylen) {
+  double* const a = reinterpret_cast<double*>(ob + voff);
+  if (lo >= BLOCKCUT && lo + 127 < BLOCKCUT + copylen) {
+    st_pair(a, z);
+  } else if (lo + 127 >= BLOCKCUT && lo < BLOCKCUT + copylen) {
+    const int p = lo + l2;
     const bool in0 = p >= BLOCKCUT && p < BLOCKCUT + copylen;
     const bool in1 = p + 1 >= BLOCKCUT && p + 1 < BLOCKCUT + copylen;
-    if (in0 && in1) *reinterpret_cast<double2*>(o + p) = z;
-    else if (in0) o[p] = z.x;
-    else if (in1) o[p + 1] = z.y;
+    if (in0 && in1) *reinterpret_cast<double2*>(a) = z;
+    else if (in0) a[0] = z.x;
+    else if (in1) a[1] = z.y;
   }
+}
+
+// A lane's part of the channel stores: pair m = t + 1024 q sits at block position 2 m.
+struct LaneStore {
+  uint32_t voff;   // byte offset of pair t: 16 t
+  int wlo;         // block position of the wave's first pair at q = 0 (wave-uniform): 128 (t >> 6)
+  int l2;          // 2 (t & 63)
+};
+__device__ __forceinline__ LaneStore lane_store(int t) { return {16u * (uint32_t)t, uni(2 * (t & ~63)), 2 * (t & 63)}; }
+// o: the channel indexed by block position (wave-uniform)
+__device__ __forceinline__ void store_q(double* o, LaneStore ls, int q, double2 z, int copylen) {
+  store_wave(reinterpret_cast<char*>(o) + 16384 * q, ls.voff, ls.wlo + 2048 * q, ls.l2, z, copylen);
 }
 
 // Store a channel's kept samples [BLOCKCUT, BLOCKCUT + copylen) from the chunk
@@ -186,11 +212,19 @@ __device__ __forceinline__ void store_pair(double* o, int m, double2 z, int copy
 // o is indexed by block position.
 __device__ __forceinline__ void store_chan(const double2* sx, double* o, int t, int copylen) {
   if (kProbeNoStore) return;
+  const LaneStore ls = lane_store(t);
 #pragma unroll
   for (int q = 0; q < 8; q++) {
     const int m = t + 1024 * q;
-    store_pair(o, m, sx[SWC(m)], copylen);
+    store_q(o, ls, q, sx[SWC(m)], copylen);
   }
+}
+
+// np.argmax order with block-relative 32-bit indices (am_beats, common.hpp)
+__device__ __forceinline__ bool am_beats32(double v, int vi, double b, int bi) {
+  const bool vn = v != v, bn = b != b;
+  if (vn || bn) return vn && (!bn || vi < bi);
+  return v > b || (v == b && vi < bi);
 }
 
 // atan(i / 64), i = 0..64 (the fast_atan2 table; copied to LDS per workgroup)
@@ -255,7 +289,7 @@ __device__ __forceinline__ void split_pairs(const CBuf x, const double2* __restr
     if (!pair_live(tid, c)) continue;
     const Slot sl = slot_of(tid, c);
     const double2 A = x[sl.p], B = x[sl.pp];
-    const double2 wk = twk[sl.p];
+    const double2 wk = *at32(twk, sl.p);
     X.a[c] = rsplit(A, B, wk);
     X.b[c] = rsplit(B, A, tw_mirror(wk));
   }
@@ -270,9 +304,9 @@ __device__ __forceinline__ void merge_pairs(const CBuf x, const double2* __restr
   for (int c = 0; c < 5; c++) {
     if (!pair_live(tid, c)) continue;
     const Slot sl = slot_of(tid, c);
-    const double2 wk = twk[sl.p];
-    const double2 Pk = cmul(D.a[c], G[sl.p]);
-    const double2 Pkp = cmul(D.b[c], G[sl.gp]);
+    const double2 wk = *at32(twk, sl.p);
+    const double2 Pk = cmul(D.a[c], *at32(G, sl.p));
+    const double2 Pkp = cmul(D.b[c], *at32(G, sl.gp));
     x[sl.p] = cmerge(Pk, Pkp, wk);
     if (sl.pp != sl.p) x[sl.pp] = cmerge(Pkp, Pk, tw_mirror(wk));
   }
@@ -334,6 +368,7 @@ __device__ __forceinline__ void demod_body(LDG_DEMOD_PARAMS) {
   if (tid < 65) s_atan[tid] = c_atan64[tid];   // ordered by the first transform's barrier
   s_tw[tw_lds_pos(tid)] = tw[2 * tid];
   const TwLds twl{s_tw};
+  const FftLane fl = fft_lane(tid);   // the transforms' lane offsets, once for all eight
   STAMP(0);
   // profiling: the launch's execution span on the constant-rate clock (first
   // workgroup start, last workgroup end), what a kernel trace reports
@@ -397,13 +432,13 @@ __device__ __forceinline__ void demod_body(LDG_DEMOD_PARAMS) {
     double x[16];
     if (fmt == 0) {
       uint4 w;
-      __builtin_memcpy(&w, cap + rel0 + 16 * tid, 16);
+      __builtin_memcpy(&w, at32(cap + rel0, 16 * tid), 16);
       const uint32_t wd[4] = {w.x, w.y, w.z, w.w};
 #pragma unroll
       for (int i = 0; i < 16; i++) x[i] = (double)((wd[i >> 2] >> (8 * (i & 3))) & 0xffu);
     } else {
       uint4 w[2];
-      __builtin_memcpy(w, reinterpret_cast<const int16_t*>(cap) + rel0 + 16 * tid, 32);
+      __builtin_memcpy(w, at32(reinterpret_cast<const int16_t*>(cap) + rel0, 16 * tid), 32);
       const uint32_t wd[8] = {w[0].x, w[0].y, w[0].z, w[0].w, w[1].x, w[1].y, w[1].z, w[1].w};
 #pragma unroll
       for (int i = 0; i < 16; i++) x[i] = (double)(int16_t)(wd[i >> 1] >> (16 * (i & 1)));
@@ -418,11 +453,12 @@ __device__ __forceinline__ void demod_body(LDG_DEMOD_PARAMS) {
     }
   }
   STAMP(1);
-  if (!(kProbe & 8)) fft8k_dif<false>(s_x, tw, twl, tid);
+  if (!(kProbe & 8)) fft8k_dif<false>(s_x, tw, twl, tid, fl);
   else __syncthreads();
   STAMP(2);
-  const bool park_lost = s_park < 0;
-  double2* const park = ospill + (int64_t)(park_lost ? PARK_SCRATCH : s_park) * M;
+  const int park_id = uni(s_park);               // the same LDS word for every lane
+  const bool park_lost = park_id < 0;
+  double2* const park = ospill + (int64_t)(park_lost ? PARK_SCRATCH : park_id) * M;
 
   // ---- 2. analytic-signal spectra and the audio carrier slices ---------------
   // Y = X * RFVideo*MTF^m; the 16384-point IFFT of Y is done as its even/odd
@@ -446,13 +482,13 @@ __device__ __forceinline__ void demod_body(LDG_DEMOD_PARAMS) {
       const bool mir = t >= 512;
       const int k = mir ? a0 + 1 + (t - 512) : a0 + t;
       const int j = mir ? a0 + 1024 - k : t;
-      double2 xk = rsplit(X_[dr_pos(k)], X_[dr_pos(M - k)], tw[k]);
+      double2 xk = rsplit(X_[dr_pos(k)], X_[dr_pos(M - k)], *at32(tw, k));
       if (mir) xk = conj2(xk);
-      const double2 al = cmul(xk, a_lfilt[j]), ar = cmul(xk, a_rfilt[j]);
+      const double2 al = cmul(xk, *at32(a_lfilt, j)), ar = cmul(xk, *at32(a_rfilt, j));
       // per slot (a later call's demod must not overwrite slices ldg_k_audio1 has not read)
       double2* as = aslice + ((int64_t)slot * MAX_BLOCKS_PER_READ + b) * 2048;   // left [0,1024), right [1024,2048)
-      as[j] = al;
-      as[1024 + j] = ar;
+      *at32(as, j) = al;
+      *at32(as + 1024, j) = ar;
     }
     __syncthreads();
     const int t = fresh(tid);
@@ -460,28 +496,29 @@ __device__ __forceinline__ void demod_body(LDG_DEMOD_PARAMS) {
     for (int c = 0; c < 5; c++) {
       if (!pair_live(t, c) || (kProbe & 16)) continue;
       const Slot sl = slot_of(t, c);
-      auto Fv = [&](int i) { return (kProbe & 128) ? make_double2(1.0 + i * 1e-9, 0.5) : F[i]; };
-      const double2 wk = twk[sl.p];
+      auto Fv = [&](int i) { return (kProbe & 128) ? make_double2(1.0 + i * 1e-9, 0.5) : *at32(F, i); };
+      const double2 wk = *at32(twk, sl.p);
       const double2 yk = cmul(X.a[c], Fv(sl.p));
       const double2 yk2 = cmul(conj2(X.b[c]), Fv(M + sl.p));
       X_[sl.p] = cadd(yk, yk2);
       if (!(kProbe & 256)) {
         const double2 o = cmulc(csub(yk, yk2), wk);
-        st_park(park + SW(sl.p), o);
+        st_park(at32(park, SW(sl.p)), o);
       }
       if (sl.pp != sl.p) {
         const double2 ykp = cmul(X.b[c], Fv(sl.pp));
         const double2 ykp2 = cmul(conj2(X.a[c]), Fv(M + sl.pp));
         X_[sl.pp] = cadd(ykp, ykp2);
-        if (!(kProbe & 256)) st_park(park + SW(sl.pp), cmulc(csub(ykp, ykp2), tw_mirror(wk)));
+        if (!(kProbe & 256)) st_park(at32(park, SW(sl.pp)), cmulc(csub(ykp, ykp2), tw_mirror(wk)));
       }
     }
   }
 
   STAMP(3);
   // (audio phase 1 -- 2 x IFFT1024 -> FM demod -- runs in ldg_k_audio1 on the
-  // slices above: the demod keeps 128 KiB of LDS, so kernels with up to 32 KiB
-  // share its CUs)
+  // slices above, on CUs the demod does not hold: a demod workgroup takes 150,560 B
+  // of the CU's 160 KiB of LDS and all 512 VGPRs of each SIMD, so nothing
+  // co-resides with it)
   // ---- 4. analytic IFFTs (even, odd) -> instantaneous phase --------------------
   // One loop body for both halves: one copy of the inverse FFT in the code (the
   // kernel would outgrow the instruction cache with every transform inlined).
@@ -494,7 +531,7 @@ __device__ __forceinline__ void demod_body(LDG_DEMOD_PARAMS) {
     if (h == 1 && tid == 0 && my_park >= 0)
       __hip_atomic_store(owners + my_park, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     double2 zr[8];
-    fft8k_dit<true, true>(s_x, tw, twl, tid, zr);
+    fft8k_dit<true, true>(s_x, tw, twl, tid, zr, fl);
     if (h == 0) {
       // the odd half returns to LDS while the even half's angles are computed:
       // every wave's park stores are complete (vmcnt) before any wave reads them
@@ -504,7 +541,7 @@ __device__ __forceinline__ void demod_body(LDG_DEMOD_PARAMS) {
       const int wbase = __builtin_amdgcn_readfirstlane(t & ~63);
 #pragma unroll
       for (int i = 0; i < 8; i++)
-        __builtin_amdgcn_global_load_lds((const void*)(park + T * i + t),
+        __builtin_amdgcn_global_load_lds((const void*)at32(park + T * i, t),
                                          (__attribute__((address_space(3))) void*)(s_x + T * i + wbase), 16, 0, 0);
     }
     STAMP(5 + 2 * h);
@@ -541,7 +578,7 @@ __device__ __forceinline__ void demod_body(LDG_DEMOD_PARAMS) {
     for (int q = 0; q < 8; q++) X_[tid + T * q] = make_double2(d0[q], d1[q]);
   }
   STAMP(9);
-  fft8k_dif<false>(s_x, tw, twl, tid);
+  fft8k_dif<false>(s_x, tw, twl, tid, fl);
   STAMP(10);
   Pairs D;
   if (!(kProbe & 64)) split_pairs(X_, twk, tid, D);
@@ -565,40 +602,33 @@ __device__ __forceinline__ void demod_body(LDG_DEMOD_PARAMS) {
     if (!(kProbe & 32)) merge_pairs(X_, twk, g_05, tid, D);
     STAMP(12);
     double2 zr[8];                               // outputs at natural positions t + T q
-    fft8k_dit<true, true>(s_x, tw, twl, tid, zr);
+    fft8k_dit<true, true>(s_x, tw, twl, tid, zr, fl);
     STAMP(13);
     const int t = fresh(tid);
     // the sync scan's per-lane powers, loaded ahead of this phase's stores
-    pl1 = iir[IIR_P1 + (t & 63)];
-    pt1 = iir[IIR_P1 + t];
-    p151 = iir[IIR_P1 + scan_d15(t & 63)];
-    p311 = iir[IIR_P1 + scan_d31(t & 63)];
+    pl1 = *at32(iir + IIR_P1, t & 63);
+    pt1 = *at32(iir + IIR_P1, t);
+    p151 = *at32(iir + IIR_P1, scan_d15(t & 63));
+    p311 = *at32(iir + IIR_P1, scan_d31(t & 63));
     // demod_05 is stored at full rate for refine_linelocs_hsync and the PAL pilot
     // windows (rebuilding those windows by the 65-tap FIR in the field kernels
     // instead measured 3.6% slower end to end, profiles/r03_z_d05_ab.txt)
     // (not past the read's video cut: its readers, refine_linelocs_hsync and the pilot
     // windows, check, FS_VCUT; uniform over the workgroup)
-    double* o = vout + (int64_t)CH_05 * vchan_stride;
+    // block position p lands at rolled position (p - 32) mod 16384: the wave's first pair
+    // sits 32 samples below its unrolled place.  Only lanes 0 - 15 of wave 0 wrap at q = 0,
+    // to [16352, 16384), which is never kept (copylen <= BLOCKSTEP), and that wave's other
+    // pairs lie below BLOCKCUT: with lo = -32 it is dropped whole.  The roll makes the waves
+    // at both ends of the kept range straddle it; they decide per lane (store_wave).
+    double* o = vout + (int64_t)CH_05 * vchan_stride - BLOCKCUT_END;
+    LaneStore ls = lane_store(t);
+    ls.wlo -= BLOCKCUT_END;
     const bool st05 = !kProbeNoStore && !(CUT && (int64_t)off >= rd.vcut);
 #pragma unroll
     for (int q = 0; q < 8; q++) {
       const int m = t + T * q;
       const double v0 = zr[q].x * inv, v1 = zr[q].y * inv;
-      if (st05) {
-        // block position p lands at rolled position (p - 32) mod 16384 (even: p0 + 1 never wraps);
-        // the wave's 64 pairs are all kept or all dropped except at the block ends
-        const int p0 = (2 * m - BLOCKCUT_END) & (BLOCKLEN - 1);
-        const int pw0 = (2 * (m & ~63) - BLOCKCUT_END) & (BLOCKLEN - 1);
-        if (pw0 >= BLOCKCUT && pw0 + 127 < BLOCKCUT + copylen) {
-          st_pair(o + p0, make_double2(v0, v1));
-        } else {
-          const bool in0 = p0 >= BLOCKCUT && p0 < BLOCKCUT + copylen;
-          const bool in1 = p0 + 1 >= BLOCKCUT && p0 + 1 < BLOCKCUT + copylen;
-          if (in0 && in1) *reinterpret_cast<double2*>(o + p0) = make_double2(v0, v1);
-          else if (in0) o[p0] = v0;
-          else if (in1) o[p0 + 1] = v1;
-        }
-      }
+      if (st05) store_q(o, ls, q, make_double2(v0, v1), copylen);
       // detector bits at UNROLLED block positions 2m, 2m + 1; lanes 8j..8j+7 (pairs
       // of 16 consecutive samples) OR their bits into lane 8j+7 (DPP row shifts)
       const uint32_t f0 = (v0 >= C.sync_lo && v0 <= C.sync_hi) ? 1u : 0u;
@@ -621,10 +651,11 @@ __device__ __forceinline__ void demod_body(LDG_DEMOD_PARAMS) {
     if (!(kProbe & 4)) iir1_bits(cur, prv, iir, &s_aux, t, pl1, pt1, p151, p311, y, &st_in);
     else for (int i = 0; i < IIR_CHUNK; i++) y[i] = (double)((cur >> i) & 1) * pl1;
     // the compact channel (chan.hpp): the kept chunks' entering states and bits
+    // (chunk t of the block is chunk cbase + t of the slot: a wave-uniform base, a 32-bit lane part)
+    const int64_t cbase = (int64_t)slot * CHUNKS_PER_SLOT + (off >> 4) - BLOCKCUT / 16;
     if (16 * t >= BLOCKCUT && 16 * t < BLOCKCUT + copylen) {
-      const int64_t g = (int64_t)slot * CHUNKS_PER_SLOT + (off >> 4) + (t - BLOCKCUT / 16);
-      sst[g] = st_in;
-      sbits[g] = cur | (prv << 16);
+      *at32(sst + cbase, t) = st_in;
+      *at32(sbits + cbase, t) = cur | (prv << 16);
     }
     // sync tiles (common.hpp SyncTile): tile j = outputs [off + 32 j, +32) =
     // block positions [1024 + 32 j, +32) = chunks of threads 64 + 2 j (+1); np.argmax
@@ -632,24 +663,27 @@ __device__ __forceinline__ void demod_body(LDG_DEMOD_PARAMS) {
     {
       const int j = (t >> 1) - 32, hf = t & 1;
       const int ntile = (copylen + 31) / 32;
+      // indices relative to the block's first output (off is added at the store: the order
+      // of two indices, and so every tie, is the same); INT_MAX: no output yet
       double v = -__builtin_inf();
-      int64_t vi = 0x7fffffffffffffffLL;
-      const int64_t n0 = (int64_t)off + 32 * j;
+      int vi = 0x7fffffff;
+      const int n0 = 32 * j;
       if (j >= 0 && j < ntile) {
 #pragma unroll
         for (int i = 0; i < IIR_CHUNK; i++) {
           const int e = 16 * hf + i;
-          if (e < copylen - 32 * j && am_beats(y[i], n0 + e, v, vi)) { v = y[i]; vi = n0 + e; }
+          if (e < copylen - 32 * j && am_beats32(y[i], n0 + e, v, vi)) { v = y[i]; vi = n0 + e; }
         }
       }
       const double ov = __shfl_xor(v, 1);
-      const int64_t oi = __shfl_xor(vi, 1);
-      if (am_beats(ov, oi, v, vi)) { v = ov; vi = oi; }
+      const int oi = __shfl_xor(vi, 1);
+      if (am_beats32(ov, oi, v, vi)) { v = ov; vi = oi; }
       if (j >= 0 && j < ntile && hf == 0) {
         SyncTile tt;
         tt.v = v;
-        tt.idx = vi;
-        stiles[(int64_t)slot * STILE_PER_SLOT + (n0 >> 5)] = tt;
+        tt.idx = vi == 0x7fffffff ? 0x7fffffffffffffffLL : (int64_t)off + vi;
+        // tile (off >> 5) + j of the slot, j = (t >> 1) - 32
+        *at32(stiles + ((int64_t)slot * STILE_PER_SLOT + (off >> 5) - 32), t >> 1) = tt;
       }
     }
   }
@@ -666,7 +700,7 @@ __device__ __forceinline__ void demod_body(LDG_DEMOD_PARAMS) {
     if (!(kProbe & 32)) merge_pairs(X_, twk, g_video, tid, D);
     STAMP(16);
     double2 zr[8];
-    if (!(kProbe & 2)) fft8k_dit<true, true>(s_x, tw, twl, tid, zr);
+    if (!(kProbe & 2)) fft8k_dit<true, true>(s_x, tw, twl, tid, zr, fl);
     else { __syncthreads(); for (int q = 0; q < 8; q++) zr[q] = s_x[tid + 1024 * q]; __syncthreads(); }
     STAMP(17);
     const int t = fresh(tid);
@@ -675,12 +709,13 @@ __device__ __forceinline__ void demod_body(LDG_DEMOD_PARAMS) {
     m15b = iir2_pow(iir + IIR_MB, scan_d15(t & 63));
     m31b = iir2_pow(iir + IIR_MB, scan_d31(t & 63));
     double* o = vout + (int64_t)CH_DEMOD * vchan_stride;
+    const LaneStore ls = lane_store(t);
 #pragma unroll
     for (int q = 0; q < 8; q++) {
       const int m = t + T * q;
       const double2 z = make_double2(zr[q].x * inv, zr[q].y * inv);
       sx[SWC(m)] = z;
-      if (!kProbeNoStore) store_pair(o, m, z, copylen);
+      if (!kProbeNoStore) store_q(o, ls, q, z, copylen);
     }
   }
   __syncthreads();
@@ -700,8 +735,8 @@ __device__ __forceinline__ void demod_body(LDG_DEMOD_PARAMS) {
     if (!(kProbe & 4)) iir2(x, h.y, h.x, iir + 3, iir + IIR_MB, &s_aux, t, mlb, mtb, m15b, m31b, y, &s_in);
     // the compact burst channel (chan.hpp): the kept chunks' entering states
     if (16 * t >= BLOCKCUT && 16 * t < BLOCKCUT + copylen) {
-      const int64_t g = (int64_t)slot * CHUNKS_PER_SLOT + (off >> 4) + (t - BLOCKCUT / 16);
-      bst[g] = make_double4(s_in.x, s_in.y, h.y, h.x);
+      const int64_t cbase = (int64_t)slot * CHUNKS_PER_SLOT + (off >> 4) - BLOCKCUT / 16;
+      *at32(bst + cbase, t) = make_double4(s_in.x, s_in.y, h.y, h.x);
     }
     if (C.n_chan > 4) {
       // PAL pilot from the same demod samples (still in x); iir2's barriers order

@@ -47,7 +47,55 @@ __host__ __device__ __forceinline__ constexpr int tw_lds_pos(int k) { return k ^
 struct TwLds {
   const double2* t;   // LDS, TW_LDS_N entries
   __device__ __forceinline__ double2 operator()(int i) const { return t[tw_lds_pos(i >> 1)]; }
+  // the entry at byte offset o = 16 tw_lds_pos(i >> 1) (FftLane)
+  __device__ __forceinline__ double2 at(uint32_t o) const {
+    return *reinterpret_cast<const double2*>(reinterpret_cast<const char*>(t) + o);
+  }
 };
+
+// A lane's LDS byte offsets in the transforms' stages.  They depend on the thread only, and
+// both directions use the same ones, so a kernel that runs several transforms computes them
+// once (fft_lane) and hands them to each; the stages then form an address with one XOR or
+// an immediate offset.  With q = tid >> 6, l = tid & 63, a1 = (l >> 3) & 1, m3 = x = l & 7:
+struct FftLane {
+  // Four registers hold the seven offsets: an LDS byte offset of the 128 KiB buffer takes 17
+  // bits, one of the 16 KiB twiddle copy 14, so each word is (twiddle offset << 17) | slot offset.
+  uint32_t w0, w1, w2, w3;
+  // stage 1: slot SW(tid & 511); point 512 r of it at + 8192 r
+  __device__ __forceinline__ uint32_t sm() const { return w0 & 0x1ffffu; }
+  // stage 2: slot 512 q + SW(l); row r at + 1024 r, odd rows at ^ 128
+  __device__ __forceinline__ uint32_t s2() const { return w1 & 0x1ffffu; }
+  // stage 3: slot 512 q + 64 (l >> 3) + 8 a1 + m3; row r at ^ 144 r
+  // (8 (r ^ a1) + (m3 ^ r) = (8 a1 + m3) ^ 9 r: the two fields do not overlap)
+  __device__ __forceinline__ uint32_t s3() const { return w2 & 0x1ffffu; }
+  // stage 4: slot 512 q + 8 (l ^ a1) + x; point r at ^ 16 r
+  __device__ __forceinline__ uint32_t s4() const { return w3; }
+  __device__ __forceinline__ uint32_t t1() const { return w0 >> 17; }   // twiddle W_8192^(q l): entry q l
+  __device__ __forceinline__ uint32_t t2() const { return w1 >> 17; }   // twiddle W^(32 l): entry 16 l
+  __device__ __forceinline__ uint32_t t3() const { return w2 >> 17; }   // twiddle W^(256 m3): entry 128 m3
+};
+__device__ __forceinline__ FftLane fft_lane(int tid) {
+  const int q = tid >> 6, l = tid & 63, a1 = (l >> 3) & 1, m3 = l & 7;
+  FftLane f;
+  f.w0 = 16u * (uint32_t)SW(tid & 511) | (16u * (uint32_t)tw_lds_pos(q * l)) << 17;
+  f.w1 = 16u * (uint32_t)(512 * q + SW(l)) | (16u * (uint32_t)tw_lds_pos(16 * l)) << 17;
+  f.w2 = 16u * (uint32_t)(512 * q + 64 * (l >> 3) + 8 * a1 + m3) | (16u * (uint32_t)tw_lds_pos(128 * m3)) << 17;
+  f.w3 = 16u * (uint32_t)(512 * q + 8 * (l ^ a1) + m3);
+  // opaque: held in registers as they are, not rebuilt from tid at every use
+  asm volatile("" : "+v"(f.w0), "+v"(f.w1), "+v"(f.w2), "+v"(f.w3));
+  return f;
+}
+// Opaque copy for one transform: what a transform derives from the words (the unpacked fields,
+// the XORed row addresses) is not carried from one inlined transform to the next, where it
+// would be spilled (as fresh() in demod.hip does for tid).
+__device__ __forceinline__ FftLane fft_lane_fresh(FftLane f) {
+  asm volatile("" : "+v"(f.w0), "+v"(f.w1), "+v"(f.w2), "+v"(f.w3));
+  return f;
+}
+// the double2 at byte offset o of the transform buffer
+__device__ __forceinline__ double2& fft_at(double2* s, uint32_t o) {
+  return *reinterpret_cast<double2*>(reinterpret_cast<char*>(s) + o);
+}
 
 // a * W16^r (conjugate twiddle for the inverse), r = 0..7
 template <bool INV> __device__ __forceinline__ double2 w16(double2 a, int r) {
@@ -74,9 +122,9 @@ __device__ __forceinline__ void wave_lds_sync() {
 
 // stage-1 twiddle for the 8 points m2 + 64 r of sub-array q: v[r] *= W_8192^(q (m2 + 64 r))
 template <bool INV>
-__device__ __forceinline__ void stage1_twiddle(double2* v, const double2* __restrict__ tw, TwLds twl, int q, int m2) {
+__device__ __forceinline__ void stage1_twiddle(double2* v, const double2* __restrict__ tw, TwLds twl, int q, uint32_t t1) {
   if (q == 0) return;   // wave-uniform
-  double2 g = twl(2 * q * m2);
+  double2 g = twl.at(t1);
   if (INV) g = conj2(g);
   v[0] = cmul(v[0], g);
 #pragma unroll
@@ -90,69 +138,66 @@ __device__ __forceinline__ void stage1_twiddle(double2* v, const double2* __rest
 // Forward (INV=false) or inverse transform, natural order in, digit-reversed out.
 // Begins and ends with a workgroup barrier, like fft_lds.
 template <bool INV>
-__device__ __forceinline__ void fft8k_dif(double2* __restrict__ s, const double2* __restrict__ tw, TwLds twl, int tid) {
+__device__ __forceinline__ void fft8k_dif(double2* __restrict__ s, const double2* __restrict__ tw, TwLds twl, int tid,
+                                          const FftLane fl_) {
+  const FftLane fl = fft_lane_fresh(fl_);
   __syncthreads();
   {
     // stage 1: radix-16 over stride 512.  Thread pair (m, b): both read all 16
     // points, thread b produces the outputs q = 2 q1 + b.
     asm volatile("" : "+v"(tid));
-    const int m = tid & 511;
     const int b = __builtin_amdgcn_readfirstlane(tid >> 9);
-    const int sm = SW(m);
     double2 u[8];
 #pragma unroll
     for (int r = 0; r < 8; r++) {
-      const double2 a = s[sm + 512 * r], c = s[sm + 512 * (r + 8)];
+      const double2 a = fft_at(s, fl.sm() + 8192u * r), c = fft_at(s, fl.sm() + 8192u * (r + 8));
       u[r] = b ? w16<INV>(csub(a, c), r) : cadd(a, c);
       if (r == 3) __builtin_amdgcn_sched_barrier(0);   // at most 8 loads in flight (register pressure)
     }
     dft8<INV>(u);
     __syncthreads();
 #pragma unroll
-    for (int q1 = 0; q1 < 8; q1++) s[512 * (2 * q1 + b) + sm] = u[q1];
+    for (int q1 = 0; q1 < 8; q1++) fft_at(s, fl.sm() + 8192u * (2 * q1) + 8192u * b) = u[q1];
   }
   __syncthreads();
   asm volatile("" : "+v"(tid));
   const int q = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l = tid & 63;
-  double2* sub = s + 512 * q;
   double2 v[8];
   {
     // stage 2: radix 8 over stride 64 inside the sub-array (slot of 64 r + l:
     // 64 r + SW(l) with bit 3 flipped for odd r)
-    const int swl = SW(l);
 #pragma unroll
-    for (int r = 0; r < 8; r++) v[r] = sub[64 * r + (swl ^ ((r & 1) << 3))];
-    stage1_twiddle<INV>(v, tw, twl, q, l);
+    for (int r = 0; r < 8; r++) v[r] = fft_at(s, (fl.s2() ^ ((r & 1u) << 7)) + 1024u * r);
+    stage1_twiddle<INV>(v, tw, twl, q, fl.t1());
     dft8<INV>(v);
-    twiddle_row_w<8, INV>(v, twl(32 * l));
+    twiddle_row_w<8, INV>(v, twl.at(fl.t2()));
 #pragma unroll
-    for (int r = 0; r < 8; r++) sub[64 * r + (swl ^ ((r & 1) << 3))] = v[r];
+    for (int r = 0; r < 8; r++) fft_at(s, (fl.s2() ^ ((r & 1u) << 7)) + 1024u * r) = v[r];
   }
   wave_lds_sync();
   {
     // stage 3: radix 8 over stride 8 inside each 64-point block (a = l >> 3)
-    const int m3 = l & 7, a1 = (l >> 3) & 1;
-    double2* p = sub + 64 * (l >> 3);
 #pragma unroll
-    for (int r = 0; r < 8; r++) v[r] = p[8 * (r ^ a1) + (m3 ^ r)];
+    for (int r = 0; r < 8; r++) v[r] = fft_at(s, fl.s3() ^ (144u * r));
     dft8<INV>(v);
-    twiddle_row_w<8, INV>(v, twl(256 * m3));
+    twiddle_row_w<8, INV>(v, twl.at(fl.t3()));
 #pragma unroll
-    for (int r = 0; r < 8; r++) p[8 * (r ^ a1) + (m3 ^ r)] = v[r];
+    for (int r = 0; r < 8; r++) fft_at(s, fl.s3() ^ (144u * r)) = v[r];
   }
   wave_lds_sync();
   {
     // stage 4: radix 8 on each 8 consecutive points
-    const int x = l & 7;
-    double2* p = sub + 8 * (l ^ ((l >> 3) & 1));
 #pragma unroll
-    for (int r = 0; r < 8; r++) v[r] = p[r ^ x];
+    for (int r = 0; r < 8; r++) v[r] = fft_at(s, fl.s4() ^ (16u * r));
     dft8<INV>(v);
 #pragma unroll
-    for (int r = 0; r < 8; r++) p[r ^ x] = v[r];
+    for (int r = 0; r < 8; r++) fft_at(s, fl.s4() ^ (16u * r)) = v[r];
   }
   __syncthreads();
+}
+template <bool INV>
+__device__ __forceinline__ void fft8k_dif(double2* __restrict__ s, const double2* __restrict__ tw, TwLds twl, int tid) {
+  fft8k_dif<INV>(s, tw, twl, tid, fft_lane(tid));
 }
 
 // Transform of a digit-reversed input (the transpose of fft8k_dif), natural order out.
@@ -163,44 +208,38 @@ __device__ __forceinline__ void fft8k_dif(double2* __restrict__ s, const double2
 // LDS reads, so the caller may write s right away.
 template <bool INV, bool OUT_REGS = false>
 __device__ __forceinline__ void fft8k_dit(double2* __restrict__ s, const double2* __restrict__ tw, TwLds twl, int tid,
-                                          double2* out = nullptr) {
+                                          double2* out, const FftLane fl_) {
+  const FftLane fl = fft_lane_fresh(fl_);
   __syncthreads();
   {
     asm volatile("" : "+v"(tid));
     const int q = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l = tid & 63;
-    double2* sub = s + 512 * q;
     double2 v[8];
     {
-      const int x = l & 7;
-      double2* p = sub + 8 * (l ^ ((l >> 3) & 1));
 #pragma unroll
-      for (int r = 0; r < 8; r++) v[r] = p[r ^ x];
+      for (int r = 0; r < 8; r++) v[r] = fft_at(s, fl.s4() ^ (16u * r));
       dft8<INV>(v);
 #pragma unroll
-      for (int r = 0; r < 8; r++) p[r ^ x] = v[r];
+      for (int r = 0; r < 8; r++) fft_at(s, fl.s4() ^ (16u * r)) = v[r];
     }
     wave_lds_sync();
     {
-      const int m3 = l & 7, a1 = (l >> 3) & 1;
-      double2* p = sub + 64 * (l >> 3);
 #pragma unroll
-      for (int r = 0; r < 8; r++) v[r] = p[8 * (r ^ a1) + (m3 ^ r)];
-      twiddle_row_w<8, INV>(v, twl(256 * m3));
+      for (int r = 0; r < 8; r++) v[r] = fft_at(s, fl.s3() ^ (144u * r));
+      twiddle_row_w<8, INV>(v, twl.at(fl.t3()));
       dft8<INV>(v);
 #pragma unroll
-      for (int r = 0; r < 8; r++) p[8 * (r ^ a1) + (m3 ^ r)] = v[r];
+      for (int r = 0; r < 8; r++) fft_at(s, fl.s3() ^ (144u * r)) = v[r];
     }
     wave_lds_sync();
     {
-      const int swl = SW(l);
 #pragma unroll
-      for (int r = 0; r < 8; r++) v[r] = sub[64 * r + (swl ^ ((r & 1) << 3))];
-      twiddle_row_w<8, INV>(v, twl(32 * l));
+      for (int r = 0; r < 8; r++) v[r] = fft_at(s, (fl.s2() ^ ((r & 1u) << 7)) + 1024u * r);
+      twiddle_row_w<8, INV>(v, twl.at(fl.t2()));
       dft8<INV>(v);
-      stage1_twiddle<INV>(v, tw, twl, q, l);
+      stage1_twiddle<INV>(v, tw, twl, q, fl.t1());
 #pragma unroll
-      for (int r = 0; r < 8; r++) sub[64 * r + (swl ^ ((r & 1) << 3))] = v[r];
+      for (int r = 0; r < 8; r++) fft_at(s, (fl.s2() ^ ((r & 1u) << 7)) + 1024u * r) = v[r];
     }
   }
   __syncthreads();
@@ -208,13 +247,11 @@ __device__ __forceinline__ void fft8k_dit(double2* __restrict__ s, const double2
     // stage 1 transposed: radix-16 over the sub-arrays.  Thread b produces the
     // outputs r = 2 r1 + b.
     asm volatile("" : "+v"(tid));
-    const int m = tid & 511;
     const int b = __builtin_amdgcn_readfirstlane(tid >> 9);
-    const int sm = SW(m);
     double2 u[8];
 #pragma unroll
     for (int q1 = 0; q1 < 8; q1++) {
-      const double2 a = s[sm + 512 * q1], c = s[sm + 512 * (q1 + 8)];
+      const double2 a = fft_at(s, fl.sm() + 8192u * q1), c = fft_at(s, fl.sm() + 8192u * (q1 + 8));
       u[q1] = b ? w16<INV>(csub(a, c), q1) : cadd(a, c);
       if (q1 == 3) __builtin_amdgcn_sched_barrier(0);
     }
@@ -226,10 +263,15 @@ __device__ __forceinline__ void fft8k_dit(double2* __restrict__ s, const double2
       return;
     } else {
 #pragma unroll
-      for (int r1 = 0; r1 < 8; r1++) s[sm + 512 * (2 * r1 + b)] = u[r1];
+      for (int r1 = 0; r1 < 8; r1++) fft_at(s, fl.sm() + 8192u * (2 * r1) + 8192u * b) = u[r1];
     }
   }
   __syncthreads();
+}
+template <bool INV, bool OUT_REGS = false>
+__device__ __forceinline__ void fft8k_dit(double2* __restrict__ s, const double2* __restrict__ tw, TwLds twl, int tid,
+                                          double2* out = nullptr) {
+  fft8k_dit<INV, OUT_REGS>(s, tw, twl, tid, out, fft_lane(tid));
 }
 
 }  // namespace ldg

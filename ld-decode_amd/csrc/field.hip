@@ -710,6 +710,12 @@ extern "C" __global__ __launch_bounds__(64) void ldg_k_linelocs(
 // demod_05 is read from the channel the demod stores.
 namespace {
 
+// np_mean of at most 128 elements (here: 20).  numpy's pairwise sum is a single block up to
+// 128 elements, pw_sum_l's first test, so this is np_mean's arithmetic without its recursion:
+// the compiler cannot see the bound, and left a call to the out-of-line pw_sum_l<7> in the
+// kernel, which cost it 16 B of scratch and the callee's registers (130 VGPRs, 3 waves per SIMD).
+__device__ __forceinline__ double np_mean_block(const double* a, int n) { return (0.0 + pw_block(a, n)) / (double)n; }
+
 template <class Src>
 __device__ void hsync_line(const Src& d05, int64_t len, const SysConst& C, int i, double v, bool lb, int lane,
                            double* s_tmp, double& out, int& flag) {
@@ -748,12 +754,12 @@ __device__ void hsync_line(const Src& d05, int64_t len, const SysConst& C, int i
         py_slice(0, 20, wl, lo, hi);
         if (lane < hi - lo) s_tmp[lane] = d05[ah + lo + lane];
         __syncthreads();
-        const double low = np_mean(s_tmp, (int)(hi - lo));
+        const double low = np_mean_block(s_tmp, (int)(hi - lo));
         __syncthreads();
         py_slice(100, 120, wl, lo, hi);
         if (lane < hi - lo) s_tmp[lane] = d05[ah + lo + lane];
         __syncthreads();
-        const double high = np_mean(s_tmp, (int)(hi - lo));
+        const double high = np_mean_block(s_tmp, (int)(hi - lo));
         double zc2;
         const int rc2 = wave_calczc_pf<3>(d05 + ah, wl, 0, (low + high) / 2, wl, lane, &zc2);
         if (rc2 != 0) { out = v; flag = 2; return; }   // None += ... -> TypeError

@@ -187,7 +187,8 @@ __device__ __forceinline__ void iir1_bits(uint32_t bits, uint32_t xm1, const dou
 // xm1, xm2 = x[16t - 1], x[16t - 2] (circular).  y[i] = y[16t + i].
 // ml, mt: C^(16 lane), C^(16 t) from the table, loaded by the caller.
 __device__ __forceinline__ double4 iir2_pow(const double* __restrict__ pw, int s) {
-  return *reinterpret_cast<const double4*>(pw + 4 * s);
+  // (pw is wave-uniform: a 32-bit lane offset, no 64-bit address arithmetic per lane)
+  return *reinterpret_cast<const double4*>(reinterpret_cast<const char*>(pw) + (uint32_t)s * 32u);
 }
 // m15, m31: C^(16 scan_d15(lane)), C^(16 scan_d31(lane)).
 __device__ __forceinline__ void iir2(const double* x, double xm1, double xm2, const double* __restrict__ cf,
