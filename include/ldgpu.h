@@ -499,6 +499,52 @@ int ldg_efmsec_last_info(ldg_ctx* ctx, ldg_efmsec_info* info);
 #define LDG_EFMSEC_ERASED 11
 int64_t ldg_efmsec_read(ldg_ctx* ctx, int what, void* dst, int64_t cap);
 
+/* ---- NTSC line services (BUILD-DEFINED: the reference snapshot decodes none of them; DESIGN.md
+ * section 7f) ----
+ * The white flag (field row 10), the video ID of IEC 61880 (row 19) and the two closed-caption
+ * bytes of EIA-608 (row 20) of NTSC fields, by an integer rule on the uint16 pixels of the one
+ * row (pixels 0 and 1, the burst flag pixels, are never read):
+ *   white flag: white_count = pixels of [100, 780) above 50 IRE; white_flag = 2 * count > 680.
+ *   captions:   cc_x = the first pixel of [270, 410) above 25 IRE after 40 pixels at or below it
+ *               (the start bit); cc_runin = rises above 25 IRE in [max(cc_x - 279, 3), cc_x - 40);
+ *               16 cells of 910 / 32 pixels follow, each read as the sum of nine pixels about its
+ *               centre against nine times 25 IRE; cc[0], cc[1] LSB first, parity bit kept.
+ *   video ID:   vid_x = the first pixel of [60, 160) above 35 IRE after 20 pixels at or below it;
+ *               22 cells of 32 pixels read the same way against 35 IRE: the reference 1, 0, then
+ *               vid_bits (14 data bits, 6 CRC bits of x^6 + x + 1 preset to ones; first cell in
+ *               bit 19).
+ * A field that is not valid or has fewer than 21 rows: white_count -1, every state 0. */
+#define LDG_LINE_ABSENT 0 /* no start found: cc_x / vid_x -1, the other members 0            */
+#define LDG_LINE_OK 1     /* captions: both bytes have odd parity; video ID: the CRC is zero   */
+#define LDG_LINE_CHECK 2  /* read, but a parity / the CRC fails                                */
+#define LDG_LINE_FRAME 3  /* captions: cc_runin outside 6..8; video ID: reference not 1, 0     */
+#define LDG_LINE_SERVICES_SIZE 36
+typedef struct ldg_line_services {
+  int32_t white_count; /* 0..680; -1: no such field                                       */
+  int32_t white_flag;  /* 0 / 1                                                           */
+  int32_t cc_state;    /* LDG_LINE_*; the bytes are reported in every state but ABSENT    */
+  int32_t cc_runin;
+  int32_t cc_x;
+  uint8_t cc[2];
+  uint8_t pad_[2];
+  int32_t vid_state;   /* LDG_LINE_*; the bits are reported in every state but ABSENT     */
+  int32_t vid_x;
+  int32_t vid_bits;    /* 20 bits                                                         */
+} ldg_line_services;
+/* The records of n live slots (as ldg_field_dropouts: distinct slots of finished decodes, n <=
+ * max_reads), from the slots' own .tbc lines, which no concealment touches.  out [n].  Synchronous,
+ * on a stream of its own: the call waits for nothing else the context has queued. */
+int ldg_field_line_services(ldg_ctx* ctx, int n, const int32_t* slots, ldg_line_services* out);
+/* The records of n packed 910 x 525 frames (any n; frame row y is row y >> 1 of the field of
+ * parity y & 1, as in ldg_stack_frames) from host memory or, frames_is_device != 0, device memory
+ * of this context's device (complete before the call: ldg_sync).  out [n][2]: top field, bottom
+ * field.  Synchronous, on the same stream and buffers of its own.
+ * Both return LDG_EINVAL (ldg_last_error names the argument; the device is not touched) on a PAL
+ * context, for n < 0 or a NULL pointer with n > 0; n == 0 does nothing.  The kernel reports
+ * through ldg_profile_read as line_services. */
+int ldg_frames_line_services(ldg_ctx* ctx, int n, const uint16_t* frames, int frames_is_device,
+                             ldg_line_services* out);
+
 /* Debug / parity access to the per-read device arrays of a live slot.
  * what: 0..4 demod channels (demod, demod_05, demod_sync, demod_burst, demod_pilot)
  *       [float64, n_out] (demod_05, demod_sync and demod_burst are expanded on request from

@@ -54,6 +54,7 @@ struct CapStream;                 // stream.inc: a capture streamed from its fil
 struct ldg_efm_state;             // efm.inc: the EFM run-length extraction's options and buffers
 struct ldg_efmdec_state;          // efmdec.inc: the EFM decode's table, carried stream and buffers
 struct ldg_efmsec_state;          // efmsec.inc: the EFM data sectors' tables, carried bytes and buffers
+struct ldg_lines_state;           // lines.inc: the NTSC line services' buffers
 
 struct ldg_ctx {
   int device = 0;
@@ -233,6 +234,7 @@ struct ldg_ctx {
   ldg_efm_state* efm = nullptr;    // EFM run lengths (efm.hip), allocated by ldg_efm_set_opts
   ldg_efmdec_state* efmdec = nullptr;   // EFM decode (efmdec.hip), allocated by ldg_efmdec_set_table
   ldg_efmsec_state* efmsec = nullptr;   // EFM data sectors (efmsec.hip), allocated on first use
+  ldg_lines_state* lines = nullptr;     // NTSC line services (lines.hip), allocated on first use
   hipEvent_t ev_fbuf[2] = {nullptr, nullptr};
   bool fbuf_recorded[2] = {false, false};
   hipEvent_t ev_tbc = nullptr;
@@ -692,6 +694,7 @@ static void stack_free(ldg_ctx* ctx);
 static void efm_free(ldg_ctx* ctx);   // efm.inc
 static void efmdec_free(ldg_ctx* ctx);   // efmdec.inc
 static void efmsec_free(ldg_ctx* ctx);   // efmsec.inc
+static void lines_free(ldg_ctx* ctx);    // lines.inc
 
 int ldg_destroy(ldg_ctx* ctx) {
   if (!ctx) return LDG_EINVAL;
@@ -740,6 +743,7 @@ int ldg_destroy(ldg_ctx* ctx) {
   efm_free(ctx);
   efmdec_free(ctx);
   efmsec_free(ctx);
+  lines_free(ctx);
   if (ctx->cap_owned) dfree(ctx->cap);
 
   for (void* p : {(void*)ctx->comb_state, (void*)ctx->comb_abl, (void*)ctx->comb_in, (void*)ctx->comb_rgb,

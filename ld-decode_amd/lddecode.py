@@ -122,6 +122,11 @@ def parse(argv=None):
                    help='samples below this level are flagged (default: the sync tip - 50 IRE)')
     p.add_argument('--dropout-hi-ire', type=float, default=None,
                    help='samples above this level are flagged (default 150 IRE)')
+    p.add_argument('--line-services', action='store_true',
+                   help="NTSC: decode the white flag (line 11), the video ID (line 20) and the closed captions "
+                        "(line 21) of every valid field (build-defined rule, DESIGN.md section 7f) into its record in "
+                        "<outfile>.json: 'lineServices': {white, whiteCount, cc, ccState, videoId, videoIdBits, "
+                        "videoIdState}; not with -p or -c")
     p.add_argument('--efm', action='store_true',
                    help='after the decode, write the EFM (digital audio) run lengths of the samples it consumed to '
                         '<outfile>.efm and a summary to <outfile>.efm.json (build-defined rule, DESIGN.md section 7c; '
@@ -210,7 +215,11 @@ def main(argv=None):
             dropouts['lo_ire'] = args.dropout_lo_ire
         if args.dropout_hi_ire is not None:
             dropouts['hi_ire'] = args.dropout_hi_ire
-    dec = GPUDecoder(system=system, device=args.device, batch=args.batch, dropouts=dropouts)
+    if args.line_services and (args.pal or args.cut):
+        print("ERROR: --line-services applies to an NTSC decode, not to -p (PAL) or -c (cut)")
+        return 1
+    dec = GPUDecoder(system=system, device=args.device, batch=args.batch, dropouts=dropouts,
+                     line_services=args.line_services)
     if args.comb_args:
         import shlex
         import comb_ntsc
@@ -489,11 +498,14 @@ def sharded(args, dec, outname, firstframe, num_frames, nextsample, req_frames, 
              'comb_args': args.comb_args, 'no_json': bool(args.no_json)}
     if dec.dropouts is not None:               # (absent when off: the manifest of a plain decode is unchanged)
         ident['dropouts'] = dec.dropouts
+    if dec.line_services:
+        ident['line_services'] = True
     man = None
     if args.manifest and os.path.exists(args.manifest):
         with open(args.manifest) as fh:
             man = json.load(fh)
-        if any(man.get(k) != v for k, v in ident.items()) or man.get('dropouts') != dec.dropouts:
+        if any(man.get(k) != v for k, v in ident.items()) or man.get('dropouts') != dec.dropouts or \
+                bool(man.get('line_services')) != dec.line_services:
             print('ERROR: %s belongs to another decode' % args.manifest)
             return 1
         if man.get('complete'):

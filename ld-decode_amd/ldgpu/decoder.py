@@ -216,10 +216,12 @@ class GPUDecoder:
     # the start probes' state before __init__ sets it: off, nothing planned or decoded
     # (_stream_fit reads it, also on a decoder the tests build without a GPU)
     probe, probe_win = False, 0
+    line_services = False
     plan_guessed = full_keys = frozenset()
     _hint_keys = ()
 
-    def __init__(self, system='NTSC', device=0, batch=32, capacity=None, log=None, dropouts=None):
+    def __init__(self, system='NTSC', device=0, batch=32, capacity=None, log=None, dropouts=None,
+                 line_services=False):
         self.rf = RFTables(system)
         self.sysp = self.rf.system
         self.batch = batch
@@ -279,6 +281,11 @@ class GPUDecoder:
         # fields over the defaults ({} = the defaults) detects every output field's runs
         # (the records' 'dropouts' key) and, with conceal, conceals them in the frames
         self.dropouts = self.ctx.set_dropout_opts(dict(dropouts)) if dropouts is not None else None
+        # NTSC line services (build-defined): every valid output field's
+        # white flag, closed captions and video ID into its record's 'lineServices' key
+        if line_services and self.sysp.name != 'NTSC':
+            raise ValueError('line_services is defined for NTSC only')
+        self.line_services = bool(line_services)
         self.plan_located = 0              # leading fields the last plan walked on decoded reads
         self.htrace = [] if os.environ.get('LDG_HOSTTRACE') else None   # (perf_counter, event, n): host timeline
         self.comb, self.comb_sink = False, None
@@ -1110,6 +1117,14 @@ class GPUDecoder:
                 for x, rec in zip(fr.field_objs, fr.fields):
                     if x.valid:
                         rec['dropouts'] = next(runs).tolist()
+        if self.line_services:
+            # likewise, from the slots' own .tbc lines (which no concealment touches)
+            objs = [x for fr in frames for x in fr.field_objs if x.valid]
+            recs = iter(self.ctx.field_line_services([x.slot for x in objs])) if objs else iter(())
+            for fr in frames:
+                for x, rec in zip(fr.field_objs, fr.fields):
+                    if x.valid:
+                        rec['lineServices'] = native.line_services_json(next(recs))
         if sink is None:
             # benchmark mode: .tbc frames (and their comb output) stay in HBM
             self.ctx.assemble_frames_device(tops, bots)

@@ -34,7 +34,8 @@ EXPORTS = ['ldg_create', 'ldg_destroy', 'ldg_last_error', 'ldg_set_filters', 'ld
            'ldg_stack_frames', 'ldg_conceal_frames', 'ldg_stack_stats',
            'ldg_efm_defaults', 'ldg_efm_set_opts', 'ldg_efm_window', 'ldg_efm_extract', 'ldg_efm_debug_read',
            'ldg_efmdec_set_table', 'ldg_efmdec_reset', 'ldg_efmdec_feed', 'ldg_efmdec_read',
-           'ldg_efmsec_enable', 'ldg_efmsec_reset', 'ldg_efmsec_feed', 'ldg_efmsec_last_info', 'ldg_efmsec_read']
+           'ldg_efmsec_enable', 'ldg_efmsec_reset', 'ldg_efmsec_feed', 'ldg_efmsec_last_info', 'ldg_efmsec_read',
+           'ldg_field_line_services', 'ldg_frames_line_services']
 STACK_MAX_SOURCES = 16            # LDG_STACK_MAX_SOURCES
 STACK_MODES = {'median': 0, 'mean': 1, 'smart-mean': 2}      # LDG_STACK_*
 STACK_STATS = ('h2d_s', 'kernel_s', 'd2h_s', 'calls')        # ldg_stack_stats, in order
@@ -100,6 +101,33 @@ class DropoutOpts(C.Structure):
 class Dropout(C.Structure):
     """ldg_dropout: pixels [startx, endx) of field row `row`."""
     _fields_ = [('row', C.c_int16), ('startx', C.c_int16), ('endx', C.c_int16), ('pad_', C.c_int16)]
+
+
+class LineServices(C.Structure):
+    """ldg_line_services: the white flag, closed captions and video ID of one NTSC field."""
+    _fields_ = [('white_count', C.c_int32), ('white_flag', C.c_int32), ('cc_state', C.c_int32),
+                ('cc_runin', C.c_int32), ('cc_x', C.c_int32), ('cc', C.c_uint8 * 2), ('pad_', C.c_uint8 * 2),
+                ('vid_state', C.c_int32), ('vid_x', C.c_int32), ('vid_bits', C.c_int32)]
+
+
+LINE_SERVICES_SIZE = 36           # LDG_LINE_SERVICES_SIZE
+LINE_ABSENT, LINE_OK, LINE_CHECK, LINE_FRAME = range(4)      # LDG_LINE_*
+
+
+def line_records(arr):
+    """The ldg_line_services of a numpy view (any shape) as a flat list of dicts of their members."""
+    return [{'white_count': wc, 'white_flag': wf, 'cc_state': cs, 'cc_runin': cr, 'cc_x': cx,
+             'cc': (int(cc[0]), int(cc[1])), 'vid_state': vs, 'vid_x': vx, 'vid_bits': vb}
+            for wc, wf, cs, cr, cx, cc, _, vs, vx, vb in arr.reshape(-1).tolist()]
+
+
+def line_services_json(d):
+    """One of line_records as the 'lineServices' of a field's metadata: the caption bytes where a start
+    bit was found, the 14 data bits of the video ID where its CRC holds."""
+    return {'white': bool(d['white_flag']), 'whiteCount': d['white_count'],
+            'cc': [d['cc'][0], d['cc'][1]] if d['cc_state'] != LINE_ABSENT else None, 'ccState': d['cc_state'],
+            'videoId': d['vid_bits'] >> 6 if d['vid_state'] == LINE_OK else None,
+            'videoIdBits': d['vid_bits'], 'videoIdState': d['vid_state']}
 
 
 class EfmOpts(C.Structure):
@@ -287,6 +315,8 @@ def load(path=None):
     lib.ldg_efmsec_last_info.argtypes = [vp, C.POINTER(EfmsecInfo)]
     lib.ldg_efmsec_read.argtypes = [vp, C.c_int, vp, C.c_int64]
     lib.ldg_efmsec_read.restype = C.c_int64
+    lib.ldg_field_line_services.argtypes = [vp, C.c_int, vp, vp]
+    lib.ldg_frames_line_services.argtypes = [vp, C.c_int, vp, C.c_int, vp]
     lib.ldg_version.restype = C.c_char_p
     lib.ldg_device_count.restype = C.c_int
     _lib = lib
@@ -714,6 +744,34 @@ class Context:
         self._check(self.lib.ldg_field_dropouts(self.h, n, sl.ctypes.data, out.ctypes.data, stride, counts.ctypes.data),
                     'ldg_field_dropouts')
         return [None if counts[i] < 0 else out[i, :counts[i], :3].copy() for i in range(n)]
+
+    # ---- NTSC line services (build-defined; include/ldgpu.h) -----
+    def field_line_services(self, slots):
+        """ldg_field_line_services: per live slot the record (line_records) of its field (white_count
+        -1: the field is not valid)."""
+        if len(slots) > self.max_reads:               # (a call takes at most max_reads slots)
+            return [r for i in range(0, len(slots), self.max_reads)
+                    for r in self.field_line_services(slots[i:i + self.max_reads])]
+        n = len(slots)
+        out = np.zeros(max(n, 1), dtype=np.dtype(LineServices))
+        sl = np.ascontiguousarray(slots, dtype=np.int32)
+        self._check(self.lib.ldg_field_line_services(self.h, n, sl.ctypes.data, out.ctypes.data),
+                    'ldg_field_line_services')
+        return line_records(out[:n])
+
+    def frames_line_services(self, frames=None, device_ptr=None, n=None):
+        """ldg_frames_line_services over packed 910 x 525 frames: a host array of n frames, or n
+        frames at a device pointer.  Returns [n][2] records (top field, bottom field)."""
+        if device_ptr is None:
+            fr = np.ascontiguousarray(frames, dtype=np.uint16).reshape(-1, 525 * 910)
+            n, ptr = fr.shape[0], fr.ctypes.data
+        else:
+            ptr = int(device_ptr)
+        out = np.zeros((max(n, 1), 2), dtype=np.dtype(LineServices))
+        self._check(self.lib.ldg_frames_line_services(self.h, n, ptr, int(device_ptr is not None), out.ctypes.data),
+                    'ldg_frames_line_services')
+        recs = line_records(out[:n])
+        return [recs[2 * i:2 * i + 2] for i in range(n)]
 
     def comb_reset(self):
         self._check(self.lib.ldg_comb_reset(self.h), 'ldg_comb_reset')
