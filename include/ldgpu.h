@@ -246,6 +246,11 @@ int ldg_set_video_cut(ldg_ctx* ctx, int64_t out_samples);
  * field whose 48 kHz audio or line refinement would reach trimmed data comes back
  * LDG_FS_VCUT like one whose video does. */
 int ldg_tail_plan(int64_t n_out, int64_t n_audio, int64_t n_audio2, int64_t vcut, int64_t out[5]);
+/* The row kernels' division by a constant (a product and two FMAs with RN(1 / c)) over n
+ * operands, for tests: out[i] = x[i] / c, with +-0, +-inf and NaN as the division gives them
+ * when guarded != 0.  LDG_EINVAL when c's significand is all ones or c is not a normal number
+ * (the kernels then divide); with x or out NULL only that check is made.  Host code. */
+int ldg_div_const(const double* x, int64_t n, double c, int guarded, double* out);
 /* The span of input-sample positions ldg_field_audio can form from a field's nlines final
  * line locations (out[0] lowest, out[1] highest; sample int(position / 64) of the 625 kHz
  * audio is read): what the device's guard holds against out[1] of ldg_tail_plan.  Host code. */

@@ -879,6 +879,9 @@ int ldg_set_filters(ldg_ctx* ctx, const ldg_params* p, const ldg_filters* f) {
   C.frame_lines = p->frame_lines; C.n_chan = ctx->system == 1 ? 5 : 4; C.audio_lo0 = p->audio_lo0;
   for (int i = 0; i < 3; i++) C.codelines[i] = p->codelines[i];
   if (C.outlinelen > MAX_OUTW || C.linelen + 200 >= 2816) { ctx->err = "unsupported line geometry"; return LDG_EINVAL; }
+  // tbc_pixel's per-context constants, by the divisions the kernel made per pixel (the same bits)
+  C.hz_ire_r = divconst_ok(C.hz_ire) ? 1.0 / C.hz_ire : 0.0;
+  C.tbc_scale = (ctx->system == 1 ? (double)(0xd300 - 0x0100) : (double)(0xc800 - 0x0400)) / (100 - C.vsync_ire);
   int rc = 0;
   rc |= upload_c128(ctx, &ctx->rfvideo, f->rfvideo, BLOCKLEN);
   rc |= upload_c128(ctx, &ctx->mtf, f->mtf, BLOCKLEN);
@@ -1002,8 +1005,14 @@ static int launch_chain(ldg_ctx* ctx, hipStream_t st, int n, const int32_t* M_) 
     LDG_LAUNCH_ON(st, "pilot_field", ldg_k_pilot_field, n, 256, M_, ctx->d_recs, ctx->d_lines, C, ctx->d_scratch,
                ctx->d_reads);
   }
-  if (!(ctx->skip >> 8 & 1)) LDG_LAUNCH_ON(st, "final_lines", ldg_k_final_lines, g_rows, FINAL_NT, M_, ctx->video, ctx->vread, ctx->vchan, C,
-             ctx->d_recs, ctx->d_lines, ctx->d_blevel, ctx->d_pic, ctx->pic_stride, ctx->d_reads);
+  if (!(ctx->skip >> 8 & 1)) {
+    if (C.hz_ire_r != 0.0)
+      LDG_LAUNCH_ON(st, "final_lines", ldg_k_final_lines, g_rows, FINAL_NT, M_, ctx->video, ctx->vread, ctx->vchan, C,
+                    ctx->d_recs, ctx->d_lines, ctx->d_blevel, ctx->d_pic, ctx->pic_stride, ctx->d_reads);
+    else
+      LDG_LAUNCH_ON(st, "final_lines", ldg_k_final_lines_div, g_rows, FINAL_NT, M_, ctx->video, ctx->vread, ctx->vchan, C,
+                    ctx->d_recs, ctx->d_lines, ctx->d_blevel, ctx->d_pic, ctx->pic_stride, ctx->d_reads);
+  }
   // (pending records become FS_VALID in ldg_k_recs_out, after all groups)
   if (int rc = check_launch(ctx, "tbc kernels")) return rc;
   return LDG_OK;
@@ -1071,6 +1080,18 @@ int ldg_tail_plan(int64_t n_out, int64_t n_audio, int64_t n_audio2, int64_t vcut
     out[3] += !a1_block_dead(b, tp.acut1);
     out[4] += !(vcut > 0 && (int64_t)b * BLOCKSTEP >= vcut);
   }
+  return LDG_OK;
+}
+
+// divconst.hpp's division by a constant over n operands, for tests: out[i] = div_const
+// (guarded != 0) or div_const_nz of x[i] with c and RN(1 / c), the sequence the row kernels
+// run.  LDG_EINVAL when c fails divconst_ok (x or out null: only that check is made).
+// Needs no context and no GPU.
+int ldg_div_const(const double* x, int64_t n, double c, int guarded, double* out) {
+  if (!divconst_ok(c) || n < 0) return LDG_EINVAL;
+  if (!x || !out) return LDG_OK;
+  const double r = 1.0 / c;
+  for (int64_t i = 0; i < n; i++) out[i] = guarded ? div_const(x[i], c, r) : div_const_nz(x[i], c, r);
   return LDG_OK;
 }
 

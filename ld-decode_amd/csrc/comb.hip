@@ -38,6 +38,7 @@
 // the chains run as verified warm-started chunks across lanes (below).
 #include <hip/hip_runtime.h>
 #include "common.hpp"
+#include "divconst.hpp"
 
 namespace ldg {
 namespace comb {
@@ -120,9 +121,15 @@ __constant__ NRTaps g_nr = {{
     1.141291975113614e-04}};
 
 __device__ __forceinline__ double clampd(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }
+// clampd for a v that is not NaN, with a result whose sign of zero is not looked at (at
+// lo = 0 a v of -0 may come back as either zero): a maximum and a minimum instead of two
+// compares and two selects
+__device__ __forceinline__ double clampd_num(double v, double lo, double hi) { return fmin(fmax(v, lo), hi); }
 
 // clp1 with the three clp0 rows staged in LDS (p = l-2, c = l, n = l+2; the
 // PAL decoder passes l-4 / l+4 and its own p_2drange = 45 * its irescale).
+// RCP: p2drange is the constant P_2DRANGE, divided by through div_const_nz (divconst.hpp).
+template <bool RCP = false>
 __device__ __forceinline__ double clp1_v(double c0, double cm, double p0, double pm, double n0, double nm,
                                          double p2drange = P_2DRANGE, bool adaptive = true);
 __device__ __forceinline__ double clp1_lds(const double* p1, const double* c1, const double* n1, int h,
@@ -130,6 +137,7 @@ __device__ __forceinline__ double clp1_lds(const double* p1, const double* c1, c
   return clp1_v(c1[h], c1[h - 1], p1[h], p1[h - 1], n1[h], n1[h - 1], p2drange, adaptive);
 }
 // the same from the six clp0 values (line l at h / h-1, l-2, l+2)
+template <bool RCP>
 __device__ __forceinline__ double clp1_v(double c0, double cm, double p0, double pm, double n0, double nm,
                                          double p2drange, bool adaptive) {
   double kp = fabs(fabs(c0) - fabs(p0));
@@ -140,8 +148,16 @@ __device__ __forceinline__ double clp1_v(double c0, double cm, double p0, double
   kn -= (fabs(c0) + fabs(nm)) * .10;
   kp /= 2;
   kn /= 2;
-  kp = clampd(1 - (kp / p2drange), 0, 1);
-  kn = clampd(1 - (kn / p2drange), 0, 1);
+  if constexpr (RCP) {
+    // kp, kn: sums and differences of integers below 2^18 and tenths of them, halved -- finite,
+    // a zero among them +0 (x - x); so 1 - kp / c is never NaN and clampd_num serves
+    constexpr double R = 1.0 / P_2DRANGE;
+    kp = clampd_num(1 - div_const_nz(kp, P_2DRANGE, R), 0, 1);
+    kn = clampd_num(1 - div_const_nz(kn, P_2DRANGE, R), 0, 1);
+  } else {
+    kp = clampd(1 - (kp / p2drange), 0, 1);
+    kn = clampd(1 - (kn / p2drange), 0, 1);
+  }
   if (!adaptive) kn = kp = 1.0;                          // -a (comb-ntsc.cxx:333)
   double sc = 1.0;
   if (kn != 0 || kp != 0) {
@@ -162,7 +178,8 @@ __device__ __forceinline__ double clp1_v(double c0, double cm, double p0, double
 __device__ __forceinline__ double u16_to_ire_of(double v) {
   const uint16_t level = (uint16_t)(int32_t)v;
   if (level == 0) return -100;
-  return -40 + ((double)level - IREBASE) / IRESCALE;
+  // level - IREBASE: an integer in [-1023, 64511], +0 at level 1024 (and -40 + -0 is -40 too)
+  return -40 + div_const_nz((double)level - IREBASE, IRESCALE, 1.0 / IRESCALE);
 }
 
 // SplitIQ's held I / Q at pixel p (0 outside [4, 840)) from the signed chroma cv.
@@ -210,13 +227,9 @@ using namespace ldg::comb;
 // steps on one lane: ~6k instead of ~30k for a 60-frame call.
 // grid: 1 workgroup of 256 threads.
 constexpr int BURST_PIECE = 40960;   // lines staged per pass (80 KiB of uint16 levels in LDS)
-// raw / IRESCALE correctly rounded from a product and one FMA correction:
-// checked equal to the division for every uint16 (tools/burst_div_check.c)
+// raw / IRESCALE (div_const_nz: an integer level, +0 at 0)
 __device__ __forceinline__ double burst_level(uint16_t raw) {
-  constexpr double INV = 1.0 / IRESCALE;
-  const double x = (double)raw;
-  const double q = x * INV;
-  return __fma_rn(__fma_rn(-q, IRESCALE, x), INV, q);
+  return div_const_nz((double)raw, IRESCALE, 1.0 / IRESCALE);
 }
 __device__ __forceinline__ double burst_step(double a, uint16_t raw) {
   const double bk = burst_level(raw);                  // comb-ntsc.cxx:560
@@ -825,26 +838,38 @@ __device__ __forceinline__ void comb_row_default(const uint16_t (*s_raw)[IN_X + 
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int l = row + O::firstline;
   KSTAMP(0, 2);
-  // Split1D's clp0 of the three lines, formed where Split2D reads it (no staging pass)
-  auto clp0 = [&](int k, int h) -> double {
-    const int r = l - 2 + 2 * k;
-    if (r < 44 || h < 4 || h >= 840) return 0.0;
-    const int avg = ((int)s_raw[k][h + 2] + (int)s_raw[k][h - 2]) / 2;   // integer average (Split1D)
-    return (double)(avg - (int)s_raw[k][h]);
-  };
   const bool invertphase = (s_raw[1][0] == 16384);
-  // (unrolled: the pixels' dependent clp1 chains -- three divisions each -- interleave)
+  // Split1D's clp0 of line l - 2 + 2 k, formed where Split2D reads it (no staging pass)
+  auto clp0i = [&](int k, int h) -> int {
+    const int r = l - 2 + 2 * k;
+    if (r < 44 || h < 4 || h >= 840) return 0;
+    const int avg = ((int)s_raw[k][h + 2] + (int)s_raw[k][h - 2]) / 2;   // integer average (Split1D)
+    return avg - (int)s_raw[k][h];
+  };
+  // Split2D reads clp0 at h and h - 1 of the three lines, so a wave takes 63 consecutive
+  // pixels per pass and forms each clp0 once: lane 0 forms those of the pixel before the 63
+  // only (lane 63's pixel of the pass before), and every lane takes its left neighbour's
+  // three by a one-lane DPP shift -- as the integers they are (0x138 = wave_shr:1).  A
+  // pixel's arithmetic is what it was; only which lane forms a clp0 changed.
+  constexpr int CV_PASSES = (836 + 62) / 63;              // pixels 4 .. 839, 63 per wave and pass
+  // (unrolled: the pixels' dependent clp1 chains -- two divisions each -- interleave)
 #pragma unroll
-  for (int u = 0; u < (CV_STRIDE + 255) / 256; u++) {
-    const int h = tid + 256 * u;
-    if (h >= CV_STRIDE) continue;
-    double cv = 0.0;
-    if (h >= 4 && h < 840) {
+  for (int u = 0; u < (CV_PASSES + 3) / 4; u++) {
+    const int j = 4 * u + wv;                             // (wave-uniform)
+    if (j >= CV_PASSES) continue;
+    const int h = 3 + 63 * j + lane;                      // lane 0: the pixel before this pass's
+    int c0[3], cm[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      c0[k] = clp0i(k, h);
+      cm[k] = __builtin_amdgcn_update_dpp(0, c0[k], 0x138, 0xf, 0xf, false);
+    }
+    if (lane >= 1 && h < 840) {
       double cavg = 0;
       cavg += 0.0 * 0.0;                                 // clpbuffer[2] * combk[2]
-      const double c1h = clp0(1, h);
+      const double c1h = (double)c0[1];
       if (h >= 18) {
-        cavg += clp1_v(c1h, clp0(1, h - 1), clp0(0, h), clp0(0, h - 1), clp0(2, h), clp0(2, h - 1), P_2DRANGE, true) * 1.0;
+        cavg += clp1_v<true>(c1h, (double)cm[1], (double)c0[0], (double)cm[0], (double)c0[2], (double)cm[2], P_2DRANGE, true) * 1.0;
         cavg += c1h * 0.0;
       } else {
         cavg += 0.0 * 0.0;
@@ -852,10 +877,12 @@ __device__ __forceinline__ void comb_row_default(const uint16_t (*s_raw)[IN_X + 
       }
       cavg /= 2;
       if (!invertphase) cavg = -cavg;
-      cv = cavg;
+      s_cv[h] = cavg;
     }
-    s_cv[h] = cv;
   }
+  // SplitIQ's cv is 0 outside [4, 840)
+  if (tid < 4) s_cv[tid] = 0.0;
+  if (tid < CV_STRIDE - 840) s_cv[840 + tid] = 0.0;
   __syncthreads();
   KSTAMP(0, 3);
   const bool fiq = l >= 44;
@@ -864,19 +891,15 @@ __device__ __forceinline__ void comb_row_default(const uint16_t (*s_raw)[IN_X + 
   {
     const int t0 = fiq ? tid - 128 : tid, nt = fiq ? 128 : 256;
     if (t0 >= 0) {
+      // comb_out_row's AdjustY with p = h + 2 in [68, 836), inside [4, 840): the held I is
+      // +-cv[p] for an even p and the held Q +-cv[p] for an odd one (held_i / held_q), and
+      // with the phase's sign (h & 3: ii, -qq, -ii, qq) each of the four cases is -cv[p].
+      // Negations are exact, so this is the same double.
       for (int h = 66 + t0; h < 834; h += nt) {
         const int p = h + 2;
-        const double yy = (p >= 4 && p < 840) ? (double)s_raw[1][p] : 0.0;
-        const double ii = held_i(s_cv, p), qq = held_q(s_cv, p);
-        double comp = 0;
-        switch (h & 3) {
-          case 0: comp = ii; break;
-          case 1: comp = -qq; break;
-          case 2: comp = -ii; break;
-          default: comp = qq; break;
-        }
-        if (invertphase) comp = -comp;
-        s_y[h] = yy + comp;
+        const double yy = (double)s_raw[1][p];
+        const double c = s_cv[p];
+        s_y[h] = yy + (invertphase ? c : -c);
       }
     }
   }
@@ -995,8 +1018,8 @@ __device__ __forceinline__ void comb_row_default(const uint16_t (*s_raw)[IN_X + 
     double y0 = 0;
 #pragma unroll
     for (int o = 0; o < 25; o++) y0 += (g_nr.b[o] / 1.0) * s_y[h + 12 - o];
-    double a = y0;
-    if (fabs(a) > O::nr_y) a = (a > 0) ? O::nr_y : -O::nr_y;
+    // (|a| > nr_y ? +-nr_y : a, of a finite sum; a -0 stays -0)
+    const double a = clampd_num(y0, -O::nr_y, O::nr_y);
     const double yv = s_y[h] - a;
     double iv = (fiq && h >= 2 && h < 838) ? s_iq[0][(h - 2) >> 1] : held_i(s_cv, h + 2);
     double qv = (fiq && h >= 3 && h < 838) ? s_iq[1][(h - 3) >> 1] : (fiq && h == 2) ? 0.0 : held_q(s_cv, h + 2);
@@ -1004,14 +1027,16 @@ __device__ __forceinline__ void comb_row_default(const uint16_t (*s_raw)[IN_X + 
     qv *= kc;
     double yi = u16_to_ire_of(yv);
     yi = (yi - O::black_ire) * kb;
-    const double qq = +(iv) / IRESCALE;
-    const double ii = +(qv) / IRESCALE;
+    // iv, qv: a chain output (or a held cv) times kc -- finite, but -0 where cv is -0
+    const double qq = div_const(+(iv), IRESCALE, 1.0 / IRESCALE);
+    const double ii = div_const(+(qv), IRESCALE, 1.0 / IRESCALE);
     double r = yi + (.956 * ii) + (.621 * qq);
     double g = yi - (.272 * ii) - (.647 * qq);
     double b = yi - (1.106 * ii) + (1.703 * qq);
-    r = clampd(r * m, 0, 65535);
-    g = clampd(g * m, 0, 65535);
-    b = clampd(b * m, 0, 65535);
+    // (finite: aburst is -1 or a mean of levels above 3; a -0 converts to 0 like +0)
+    r = clampd_num(r * m, 0, 65535);
+    g = clampd_num(g * m, 0, 65535);
+    b = clampd_num(b * m, 0, 65535);
     out[x * 3 + 0] = (uint16_t)r;
     out[x * 3 + 1] = (uint16_t)g;
     out[x * 3 + 2] = (uint16_t)b;

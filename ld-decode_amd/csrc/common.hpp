@@ -80,6 +80,8 @@ struct SysConst {
   double fsc_mhz;
   double sy_b0, sy_p;             // FPsync recurrence (iir.hpp): b0, p = -a1
   double bu_b0, bu_b1, bu_b2, bu_a1, bu_a2;   // Fburst recurrence
+  double hz_ire_r;                // RN(1 / hz_ire) for div_const (divconst.hpp); 0: divide (hz_ire fails divconst_ok)
+  double tbc_scale;               // tbc_pixel's output scale, (0xc800 - 0x0400 | 0xd300 - 0x0100) / (100 - vsync_ire)
   int32_t system;                 // 0 NTSC, 1 PAL
   int32_t linelen;                // rf.linelen (2542 / 2560)
   int32_t outlinelen;             // 910 / 1135

@@ -18,6 +18,8 @@
 #include "tail.hpp"
 #include "pyops.hpp"
 #include "chan.hpp"
+#include "divconst.hpp"
+#include <type_traits>
 
 using namespace ldg;
 
@@ -331,8 +333,9 @@ __device__ __forceinline__ int burst_line(const double* __restrict__ video, int6
   // the burst statistics on the whole wave (numpy's pairwise sums via wave_pw_block)
   double* ba = s_ba;
   double* tt = s_t;
-  const double hzs = 1700000 / 140.0;
-  const double m = (0.0 + wave_pw_block(ba, 40, lane)) / 40.0;
+  // (the divisions by 40 and by hzs through div_const: the same quotients, NaN and inf included)
+  constexpr double hzs = 1700000 / 140.0, hzs_r = 1.0 / hzs, r40 = 1.0 / 40.0;
+  const double m = div_const(0.0 + wave_pw_block(ba, 40, lane), 40.0, r40);
   double v = 0.0, amx = 0.0;
   if (lane < 40) { v = ba[lane] - m; amx = fabs(v); }
   for (int o = 32; o > 0; o >>= 1) amx = fmax(amx, __shfl_xor(amx, o));   // fmax drops NaNs, as the loop did
@@ -343,10 +346,10 @@ __device__ __forceinline__ int burst_line(const double* __restrict__ video, int6
   const float lf = (float)mx;
   const double lv = (double)lf;               // numpy-1: float32 element promoted to float64
   // np.std(ba)
-  const double m2 = (0.0 + wave_pw_block(ba, 40, lane)) / 40.0;
+  const double m2 = div_const(0.0 + wave_pw_block(ba, 40, lane), 40.0, r40);
   if (lane < 40) { const double d = ba[lane] - m2; tt[lane] = d * d; }
   __syncthreads();
-  const double sd = sqrt((0.0 + wave_pw_block(tt, 40, lane)) / 40.0);
+  const double sd = sqrt(div_const(0.0 + wave_pw_block(tt, 40, lane), 40.0, r40));
   // the zero-crossing walk (lddecode_core.py:1089-1104): every start position's
   // crossing (calczc over <= 11 samples) on its own lane; the walk from 0 visits
   // the first qualifying position at or after the previous one's int(zc) + 1,
@@ -380,7 +383,7 @@ __device__ __forceinline__ int burst_line(const double* __restrict__ video, int6
   if (lane != 0) return 0;
   double p0 = 0.0, p1 = 0.0;
   float out_level = lf;
-  if (((lv / hzs) > 30) || (sd / hzs) < 3) {
+  if ((div_const(lv, hzs, hzs_r) > 30) || div_const(sd, hzs, hzs_r) < 3) {
     out_level = 0.0f;
   } else if (!(nF < 3 || nT < 3)) {
     // mean of each group's [1:-1] (np.array of the list, pairwise sum)
@@ -620,13 +623,17 @@ struct ChanSrc {
   }
 };
 
-// .tbc pixel of one resampled value (lddecode_core.py:1139-1142 NTSC, :1030-1035 PAL)
+// .tbc pixel of one resampled value (lddecode_core.py:1139-1142 NTSC, :1030-1035 PAL).
+// RCP: C.hz_ire_r holds hz_ire's reciprocal (the host checked divconst_ok).
+template <bool RCP>
 __device__ __forceinline__ uint16_t tbc_pixel(double v, double wow, const SysConst& C) {
   const bool pal = C.system == 1;
-  const double scale_ = pal ? (double)(0xd300 - 0x0100) / (100 - C.vsync_ire)
-                            : (double)(0xc800 - 0x0400) / (100 - C.vsync_ire);
+  const double scale_ = C.tbc_scale;                      // (0xc800 - 0x0400) / (100 - vsync_ire), the host's division
   const double base = pal ? 256.0 : 1024.0;
-  double red = ((v * wow) - C.ire0) / C.hz_ire;           // the reference divides (:1139)
+  // the reference divides (:1139): the correctly rounded quotient, NaN and +-inf (a demod
+  // sample can be either) as the division gives them
+  const double num = (v * wow) - C.ire0;
+  double red = RCP ? div_const(num, C.hz_ire, C.hz_ire_r) : num / C.hz_ire;
   red -= C.vsync_ire;
   double px = (red * scale_) + base;
   if (px != px) px = 0.0;
@@ -636,7 +643,8 @@ __device__ __forceinline__ uint16_t tbc_pixel(double v, double wow, const SysCon
 #ifndef LDG_FINAL_WAVES
 #define LDG_FINAL_WAVES 6
 #endif
-// (6 waves per SIMD: 78 VGPRs, six line workgroups per CU, 138 KiB of LDS)
+// (6 waves per SIMD: 75 VGPRs, six line workgroups per CU, 138 KiB of LDS)
+template <bool RCP>
 __device__ __forceinline__ void final_lines_body(
     const int32_t* __restrict__ smap, const double* __restrict__ video, int64_t vread_stride, int64_t vchan_stride,
     SysConst C, FieldRec* __restrict__ recs, const double* __restrict__ lines, const float* __restrict__ blevel,
@@ -685,7 +693,7 @@ __device__ __forceinline__ void final_lines_body(
     for (int o0 = 0; o0 < W; o0 += oc) {
       const int o1 = o0 + oc < W ? o0 + oc : W;
       const int rc = spline_block<FINAL_NT>(ChanSrc{dm}, len, begin, end, W, o0, o1, tid, U.Wn,
-                                            [&](int o, double v) { out[o] = tbc_pixel(v, wow, C); });
+                                            [&](int o, double v) { out[o] = tbc_pixel<RCP>(v, wow, C); });
       if (rc < 0) {
         if (tid == 0) R->status = FS_TBC;
         return;
@@ -741,59 +749,79 @@ __device__ __forceinline__ void final_lines_body(
   auto ct = [&](int t) { return t < 16 ? S.ct[t] : kCtInf; };
   // (the Thomas coefficient c_t is re-read where used: it is constant past t = 16,
   // and holding it per row would cost 22 VGPRs -- a wave per SIMD of occupancy)
+  // Two things are the same for every thread of a wave (w0: its first thread): whether all
+  // 64 own FINAL_CHMAX rows -- every wave of a nominal line but the one that holds the line's
+  // end -- and whether its rows lie past 16, where c_t is the constant.  Such a wave runs the
+  // five sweeps without the per-row predicates and without the LDS read and select of c_t;
+  // the arithmetic of a row is the same in each form.
+  const int w0 = __builtin_amdgcn_readfirstlane(tid);
+  const bool wfull = CH == FINAL_CHMAX && (w0 + 64) * FINAL_CHMAX <= T;
+  const bool winf = w0 * CH >= 16;
+  auto sweeps = [&](auto&& f) {
+    if (wfull && winf) f(std::true_type{});
+    else f(std::false_type{});
+  };
   double rr[FINAL_CHMAX], dd[FINAL_CHMAX];
-#pragma unroll
-  for (int q = 0; q < FINAL_CHMAX; q++) {
-    if (q < nq) {
-      const int t = t0 + q;
-      double r = 6.0 * ((yv[q + 2] - yv[q + 1]) - (yv[q + 1] - yv[q]));
-      if (t == 0) r -= BL;
-      if (t == T - 1) r -= BR;
-      rr[q] = r;
-    }
-  }
-  auto cc = [&](int q) { return ct(t0 + q); };
-  // forward sweep: d -> -c d + c r
   double A = 1.0, B = 0.0;
+  sweeps([&](auto fast) {
+    constexpr bool F = decltype(fast)::value;             // all rows live, c_t = kCtInf
 #pragma unroll
-  for (int q = 0; q < FINAL_CHMAX; q++) {
-    if (q < nq) {
-      const double c = cc(q);
-      A = -c * A;
-      B = (rr[q] - B) * c;
+    for (int q = 0; q < FINAL_CHMAX; q++) {
+      if (F || q < nq) {
+        const int t = t0 + q;
+        double r = 6.0 * ((yv[q + 2] - yv[q + 1]) - (yv[q + 1] - yv[q]));
+        if (!F && t == 0) r -= BL;
+        if (t == T - 1) r -= BR;
+        rr[q] = r;
+      }
     }
-  }
+    // forward sweep: d -> -c d + c r
+#pragma unroll
+    for (int q = 0; q < FINAL_CHMAX; q++) {
+      if (F || q < nq) {
+        const double c = F ? kCtInf : ct(t0 + q);
+        A = -c * A;
+        B = (rr[q] - B) * c;
+      }
+    }
+  });
   double dprev = block_affine_carry<FINAL_NT, false>(A, B, tid, S);
   KSTAMP(1, 2);
+  sweeps([&](auto fast) {
+    constexpr bool F = decltype(fast)::value;             // all rows live, c_t = kCtInf
 #pragma unroll
-  for (int q = 0; q < FINAL_CHMAX; q++) {
-    if (q < nq) {
-      const double d = (rr[q] - dprev) * cc(q);
-      dd[q] = d;
-      dprev = d;
+    for (int q = 0; q < FINAL_CHMAX; q++) {
+      if (F || q < nq) {
+        const double d = (rr[q] - dprev) * (F ? kCtInf : ct(t0 + q));
+        dd[q] = d;
+        dprev = d;
+      }
     }
-  }
-  // back substitution: M -> d - c M, top down
-  A = 1.0; B = 0.0;
+    // back substitution: M -> d - c M, top down
+    A = 1.0; B = 0.0;
 #pragma unroll
-  for (int q = FINAL_CHMAX - 1; q >= 0; q--) {
-    if (q < nq) {
-      const double c = cc(q);
-      A = -c * A;
-      B = dd[q] - c * B;
+    for (int q = FINAL_CHMAX - 1; q >= 0; q--) {
+      if (F || q < nq) {
+        const double c = F ? kCtInf : ct(t0 + q);
+        A = -c * A;
+        B = dd[q] - c * B;
+      }
     }
-  }
+  });
   double Mnext = block_affine_carry<FINAL_NT, true>(A, B, tid, S);
   KSTAMP(1, 3);
   double* ms = S.ms;
+  sweeps([&](auto fast) {
+    constexpr bool F = decltype(fast)::value;             // all rows live, c_t = kCtInf
 #pragma unroll
-  for (int q = FINAL_CHMAX - 1; q >= 0; q--) {
-    if (q < nq) {
-      const double M = dd[q] - cc(q) * Mnext;
-      ms[lo + t0 + q] = M;
-      Mnext = M;
+    for (int q = FINAL_CHMAX - 1; q >= 0; q--) {
+      if (F || q < nq) {
+        const double M = dd[q] - (F ? kCtInf : ct(t0 + q)) * Mnext;
+        ms[lo + t0 + q] = M;
+        Mnext = M;
+      }
     }
-  }
+  });
   __syncthreads();
   if (tid == 0) {
     ms[1] = M1;
@@ -828,7 +856,7 @@ __device__ __forceinline__ void final_lines_body(
     const double a = (double)(k + 1) - x, b = x - (double)k;
     const double m6 = Mk * kSixth, m16 = Mk1 * kSixth;
     const double v = m6 * a * a * a + m16 * b * b * b + (yk[e] - m6) * a + (yk1[e] - m16) * b;
-    out[o] = tbc_pixel(v, wow, C);
+    out[o] = tbc_pixel<RCP>(v, wow, C);
   }
   KSTAMP(1, 5);
   // NTSC burst flag pixels (threads 0 / 1 wrote pixels 0 / 1 above)
@@ -847,7 +875,15 @@ extern "C" __global__ __launch_bounds__(FINAL_NT, LDG_FINAL_WAVES) void ldg_k_fi
     const int32_t* __restrict__ smap, const double* __restrict__ video, int64_t vread_stride, int64_t vchan_stride,
     SysConst C, FieldRec* __restrict__ recs, const double* __restrict__ lines, const float* __restrict__ blevel,
     uint16_t* __restrict__ pic, int64_t pic_stride, const ReadDesc* __restrict__ reads) {
-  final_lines_body(smap, video, vread_stride, vchan_stride, C, recs, lines, blevel, pic, pic_stride, reads);
+  final_lines_body<true>(smap, video, vread_stride, vchan_stride, C, recs, lines, blevel, pic, pic_stride, reads);
+}
+// the same with tbc_pixel's division kept, for a context whose hz_ire has no usable reciprocal
+// (C.hz_ire_r == 0: divconst.hpp's condition on the divisor)
+extern "C" __global__ __launch_bounds__(FINAL_NT, LDG_FINAL_WAVES) void ldg_k_final_lines_div(
+    const int32_t* __restrict__ smap, const double* __restrict__ video, int64_t vread_stride, int64_t vchan_stride,
+    SysConst C, FieldRec* __restrict__ recs, const double* __restrict__ lines, const float* __restrict__ blevel,
+    uint16_t* __restrict__ pic, int64_t pic_stride, const ReadDesc* __restrict__ reads) {
+  final_lines_body<false>(smap, video, vread_stride, vchan_stride, C, recs, lines, blevel, pic, pic_stride, reads);
 }
 
 // Mark reads still pending after the whole chain as valid.

@@ -25,7 +25,7 @@ EXPORTS = ['ldg_create', 'ldg_destroy', 'ldg_last_error', 'ldg_set_filters', 'ld
            'ldg_profile_read', 'ldg_synth_capture', 'ldg_capture_download', 'ldg_comb_ntsc_async', 'ldg_sync', 'ldg_demod_isolated', 'ldg_demod_isolated_ex', 'ldg_comb_set_opts', 'ldg_output_async', 'ldg_output_wait',
            'ldg_host_alloc', 'ldg_host_free',
            'ldg_archive_fields', 'ldg_archive_audio', 'ldg_decode_reads_async', 'ldg_decode_reads_async2',
-           'ldg_set_video_cut', 'ldg_tail_plan', 'ldg_audio_reach', 'ldg_decode_reads_wait',
+           'ldg_set_video_cut', 'ldg_tail_plan', 'ldg_audio_reach', 'ldg_div_const', 'ldg_decode_reads_wait',
            'ldg_field_audio_async', 'ldg_field_audio_collect', 'ldg_comb_ntsc3d', 'ldg_cx_create', 'ldg_cx_destroy', 'ldg_cx_process', 'ldg_comb_pal', 'ldg_comb_set_state', 'ldg_profile_spans', 'ldg_profile_spans_union', 'ldg_profile_span_table',
            'ldg_audio_offsets', 'ldg_comb_async', 'ldg_debug_rf_table',
            'ldg_stream_open', 'ldg_stream_release', 'ldg_stream_seek', 'ldg_stream_window', 'ldg_stream_stats',
@@ -262,6 +262,7 @@ def load(path=None):
     lib.ldg_decode_reads_async2.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     lib.ldg_set_video_cut.argtypes = [vp, C.c_int64]
     lib.ldg_tail_plan.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp]
+    lib.ldg_div_const.argtypes = [vp, C.c_int64, C.c_double, C.c_int, vp]
     lib.ldg_audio_reach.argtypes = [vp, C.c_int, C.c_int, C.c_double, vp]
     lib.ldg_decode_reads_wait.argtypes = [vp, vp]
     lib.ldg_archive_fields.argtypes = [vp, C.c_int, vp, C.c_int64]
@@ -1024,6 +1025,22 @@ def tail_plan(n_out, n_audio, n_audio2, vcut):
         raise ValueError('ldg_tail_plan: %d' % rc)
     a1, a2, l2, l1, l05 = (int(v) for v in out)
     return (None if a1 < 0 else a1, None if a2 < 0 else a2, l2, l1, l05)
+
+
+def div_const(x, c, guarded=True):
+    """ldg_div_const: x / c by the row kernels' product-and-two-FMAs sequence (guarded: +-0,
+    +-inf and NaN as the division gives them).  ValueError when c has no usable reciprocal.
+    Host code, no device needed."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    out = np.empty_like(x)
+    if load().ldg_div_const(x.ctypes.data, x.size, float(c), int(bool(guarded)), out.ctypes.data) != 0:
+        raise ValueError('ldg_div_const: no reciprocal form for %r' % c)
+    return out
+
+
+def divconst_ok(c):
+    """True when ldg_div_const (and the kernels) divide by c through its reciprocal."""
+    return load().ldg_div_const(None, 0, float(c), 1, None) == 0
 
 
 def audio_reach(lines, linecount, linelen):

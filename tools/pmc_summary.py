@@ -61,15 +61,18 @@ def derived(c):
         d['lds_array_busy_frac'] = c['SQ_LDS_IDX_ACTIVE'] / c['SQ_BUSY_CU_CYCLES']
     if c.get('SQ_LDS_IDX_ACTIVE') and 'SQ_LDS_BANK_CONFLICT' in c:
         d['lds_conflict_cycles_per_active'] = c['SQ_LDS_BANK_CONFLICT'] / c['SQ_LDS_IDX_ACTIVE']
-    if 'SQ_INSTS_VALU_FMA_F64' in c:
-        d['fp64_flops_per_launch'] = 64 * (2 * c['SQ_INSTS_VALU_FMA_F64'] + c.get('SQ_INSTS_VALU_MUL_F64', 0) +
-                                           c.get('SQ_INSTS_VALU_ADD_F64', 0))
+    # the FP64 figures need all three counters: from a pass that took one of them alone they
+    # would read as a smaller share, not as a missing one
+    f64 = all(k in c for k in ('SQ_INSTS_VALU_FMA_F64', 'SQ_INSTS_VALU_MUL_F64', 'SQ_INSTS_VALU_ADD_F64'))
+    if f64:
+        d['fp64_flops_per_launch'] = 64 * (2 * c['SQ_INSTS_VALU_FMA_F64'] + c['SQ_INSTS_VALU_MUL_F64'] +
+                                           c['SQ_INSTS_VALU_ADD_F64'])
     if 'SQ_INSTS_VALU' in c and c.get('GRBM_GUI_ACTIVE'):
         d['valu_issue_frac'] = c['SQ_INSTS_VALU'] * 4 / (1024 * c['GRBM_GUI_ACTIVE'] / 8)
         d['gpu_cycles_per_xcd'] = c['GRBM_GUI_ACTIVE'] / 8
-    if 'SQ_INSTS_VALU_FMA_F64' in c and 'SQ_INSTS_VALU' in c:
-        d['fp64_share_of_valu_insts'] = (c['SQ_INSTS_VALU_FMA_F64'] + c.get('SQ_INSTS_VALU_MUL_F64', 0) +
-                                         c.get('SQ_INSTS_VALU_ADD_F64', 0)) / c['SQ_INSTS_VALU']
+    if f64 and 'SQ_INSTS_VALU' in c:
+        d['fp64_share_of_valu_insts'] = (c['SQ_INSTS_VALU_FMA_F64'] + c['SQ_INSTS_VALU_MUL_F64'] +
+                                         c['SQ_INSTS_VALU_ADD_F64']) / c['SQ_INSTS_VALU']
     if 'SQ_INSTS_LDS_LOAD_BANDWIDTH' in c:
         d['lds_load_bytes'] = 64 * c['SQ_INSTS_LDS_LOAD_BANDWIDTH']
         d['lds_store_bytes'] = 64 * c.get('SQ_INSTS_LDS_STORE_BANDWIDTH', 0)
