@@ -963,8 +963,8 @@ static unsigned long long* span_slot(ldg_ctx* ctx) {
 static int launch_demod(ldg_ctx* ctx, hipStream_t st, int n, const int32_t* M_) {
   const SysConst C = ctx->C;
   LDG_LAUNCH_ON(st, "demod", ldg_k_demod, n * MAX_BLOCKS_PER_READ, 1024, M_, ctx->d_reads, ctx->cap, ctx->cap_first,
-             ctx->cap_nsamp, ctx->cap_ring, ctx->fmt, ctx->tw, ctx->twk, ctx->rf_cur, ctx->fvideo, ctx->f05, ctx->iirtab, ctx->alf, ctx->arf, C, ctx->video, ctx->vread, ctx->vchan, ctx->audio1, ctx->a1read,
-             ctx->a1chan, ctx->d_status, ctx->d_ospill, ++ctx->park_epoch, ctx->d_stile, ctx->d_aslice,
+             ctx->cap_nsamp, ctx->cap_ring, ctx->fmt, ctx->tw, ctx->twk, ctx->rf_cur, ctx->fvideo, ctx->f05, ctx->iirtab, ctx->alf, ctx->arf, C, ctx->video, ctx->vread, ctx->vchan,
+             ctx->d_status, ctx->d_ospill, ++ctx->park_epoch, ctx->d_stile, ctx->d_aslice,
              ctx->d_sst, ctx->d_sbits, ctx->d_bst, span_slot(ctx));
   return check_launch(ctx, "ldg_k_demod");
 }
@@ -1259,7 +1259,7 @@ int ldg_decode_reads_async2(ldg_ctx* ctx, int n, const int64_t* read_starts, con
     const SysConst C = ctx->C;
     LDG_LAUNCH_ON(s, "demod_probe", ldg_k_demod_probe, np, 1024, dps, ctx->d_preads, ctx->cap, ctx->cap_first,
                   ctx->cap_nsamp, ctx->cap_ring, ctx->fmt, ctx->tw, ctx->twk, ctx->rf_cur, ctx->fvideo, ctx->f05, ctx->iirtab,
-                  ctx->alf, ctx->arf, C, ctx->video, ctx->vread, ctx->vchan, ctx->audio1, ctx->a1read, ctx->a1chan,
+                  ctx->alf, ctx->arf, C, ctx->video, ctx->vread, ctx->vchan,
                   ctx->d_status, ctx->d_ospill, ++ctx->park_epoch, ctx->d_stile, ctx->d_aslice, ctx->d_sst,
                   ctx->d_sbits, ctx->d_bst, nullptr);
     LDG_LAUNCH_ON(s, "probe_pick", ldg_k_probe_pick, np, 64, dps, ctx->d_preads, ctx->d_reads, ctx->d_status,
@@ -2256,7 +2256,7 @@ int ldg_demod_isolated_ex(ldg_ctx* ctx, int n, const int32_t* slots, int iters, 
     (variant ? ldg_k_demod_iso_cut : ldg_k_demod_iso)<<<n * MAX_BLOCKS_PER_READ, 1024, 0, st>>>(
           ctx->d_isomap, ctx->d_reads, ctx->cap, ctx->cap_first, ctx->cap_nsamp, ctx->cap_ring, ctx->fmt, ctx->tw, ctx->twk,
           ctx->rf_iso, ctx->fvideo, ctx->f05, ctx->iirtab, ctx->alf, ctx->arf, C,
-          ctx->video, ctx->vread, ctx->vchan, ctx->audio1, ctx->a1read, ctx->a1chan, ctx->d_status, ctx->d_ospill,
+          ctx->video, ctx->vread, ctx->vchan, ctx->d_status, ctx->d_ospill,
           ++ctx->park_epoch, ctx->d_stile, ctx->d_aslice, ctx->d_sst, ctx->d_sbits, ctx->d_bst, nullptr);
     step(hipEventRecord(ev[2 * k + 1], st));
   }

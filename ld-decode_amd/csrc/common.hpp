@@ -116,6 +116,36 @@ __device__ __forceinline__ bool am_beats(double v, int64_t vi, double b, int64_t
 // SIMD arbiter issues their serial chains first (demod waves fill the gaps).
 __device__ __forceinline__ void prio_latency() { __builtin_amdgcn_s_setprio(3); }
 
+// Kernel arguments read where they are used.  Every parameter a kernel's body names is loaded
+// at the entry and held in SGPRs to its last use; a kernel with a long list and SysConst by
+// value runs out of them and spills into vector lanes (v_writelane / v_readlane: VALU
+// instructions).  Such a kernel states its list once, as
+//   #define LIST(P, V, L)  P(type, name) ... V(type, name) ... L(type, name)
+// (P a __restrict__ pointer, V a value, L the last pointer), takes LDG_KERNEL_PARAMS(LIST) as
+// its parameters and declares `struct Kargs { LDG_KARG_FIELDS(LIST) };`, the same list as a
+// struct: the kernarg segment's layout, every argument at its natural alignment.  An argument
+// that only one phase needs is then read in that phase with LDG_KARG(Kargs, name), a scalar
+// load from the launch's own kernarg segment (so nothing is shared between launches), and the
+// parameter of that name is left unnamed in the body.
+#define LDG_KP_P(T, n) T *__restrict__ n,
+#define LDG_KP_V(T, n) T n,
+#define LDG_KP_L(T, n) T *__restrict__ n
+#define LDG_KF_P(T, n) T* n;
+#define LDG_KF_V(T, n) T n;
+#define LDG_KA_P(T, n) n,
+#define LDG_KA_L(T, n) n
+#define LDG_KERNEL_PARAMS(LIST) LIST(LDG_KP_P, LDG_KP_V, LDG_KP_L)
+#define LDG_KERNEL_ARGS(LIST) LIST(LDG_KA_P, LDG_KA_P, LDG_KA_L)   // the names, to hand the list on
+#define LDG_KARG_FIELDS(LIST) LIST(LDG_KF_P, LDG_KF_V, LDG_KF_P)
+#define LDG_KARG(KARGS, name) \
+  (((const __attribute__((address_space(4))) KARGS*)__builtin_amdgcn_kernarg_segment_ptr())->name)
+// a pointer read that way is a global one: said here, or its accesses become flat ones
+template <class Tp>
+__device__ __forceinline__ Tp* karg_global(Tp* p) {
+  return (Tp*)(__attribute__((address_space(1))) Tp*)p;
+}
+#define LDG_KARG_PTR(KARGS, name) ldg::karg_global(LDG_KARG(KARGS, name))
+
 }  // namespace ldg
 
 // The optical-flow fields of the 3D comb with flow (flow.hip, comb.hip): 252 x 840

@@ -338,22 +338,37 @@ __device__ unsigned long long g_stamps[LDG_STAMP_BLOCKS][32];
 // them from its start; ring > 0 (a streamed capture, ldg_stream_open): cap is a ring of
 // `ring` bytes (a multiple of every format's packing group) where the capture's byte b lives
 // at b mod ring, followed by a mirror of its first bytes, so one block is contiguous.
-#define LDG_DEMOD_PARAMS                                                                                          \
-  const int32_t *__restrict__ smap, const ReadDesc *__restrict__ reads, const uint8_t *__restrict__ cap,          \
-      int64_t cap_first, int64_t cap_nsamp, int64_t ring, int fmt, const double2 *__restrict__ tw,               \
-      const double2 *__restrict__ twk, const double2 *__restrict__ rf_filt, const double2 *__restrict__ g_video,  \
-      const double2 *__restrict__ g_05, const double *__restrict__ iir, const double2 *__restrict__ a_lfilt,      \
-      const double2 *__restrict__ a_rfilt, SysConst C, double *__restrict__ video, int64_t vread_stride,          \
-      int64_t vchan_stride, double *__restrict__ audio1, int64_t aread_stride, int64_t achan_stride,              \
-      int32_t *__restrict__ status, double2 *__restrict__ ospill, unsigned long long park_epoch,                 \
-      SyncTile *__restrict__ stiles,                                                                             \
-      double2 *__restrict__ aslice, double *__restrict__ sst, uint32_t *__restrict__ sbits,                      \
-      double4 *__restrict__ bst, unsigned long long *__restrict__ span
-#define LDG_DEMOD_ARGS                                                                                            \
-  smap, reads, cap, cap_first, cap_nsamp, ring, fmt, tw, twk, rf_filt, g_video, g_05, iir, a_lfilt, a_rfilt, C, video, \
-      vread_stride, vchan_stride, audio1, aread_stride, achan_stride, status, ospill, park_epoch, stiles, aslice,  \
-      sst, sbits,                                                                                                 \
-      bst, span
+//
+// The argument list, once (common.hpp, LDG_KERNEL_PARAMS): an argument one phase uses is read
+// from the kernarg segment in that phase, DK / DKP below.  With the whole list named by the body,
+// and so live from the entry, the kernel ran out of SGPRs: 45 spilled into vector lanes, 160
+// v_writelane / v_readlane among its VALU instructions.  What the body still names is
+// what the entry uses, and the read-only tables the whole kernel reads (tw, twk, iir), which
+// keep their __restrict__: their wave-uniform loads stay scalar loads.
+#define LDG_DEMOD_ARG_LIST(P, V, L)                                                                    \
+  P(const int32_t, smap) P(const ReadDesc, reads) P(const uint8_t, cap) V(int64_t, cap_first)         \
+  V(int64_t, cap_nsamp) V(int64_t, ring) V(int, fmt) P(const double2, tw) P(const double2, twk)       \
+  P(const double2, rf_filt) P(const double2, g_video) P(const double2, g_05) P(const double, iir)     \
+  P(const double2, a_lfilt) P(const double2, a_rfilt) V(SysConst, C) P(double, video)                 \
+  V(int64_t, vread_stride) V(int64_t, vchan_stride) P(int32_t, status) P(double2, ospill)             \
+  V(unsigned long long, park_epoch) P(SyncTile, stiles) P(double2, aslice) P(double, sst)             \
+  P(uint32_t, sbits) P(double4, bst) L(unsigned long long, span)
+#define LDG_DEMOD_PARAMS LDG_KERNEL_PARAMS(LDG_DEMOD_ARG_LIST)
+struct DemodKargs {
+  LDG_KARG_FIELDS(LDG_DEMOD_ARG_LIST)
+};
+#define DK(name) LDG_KARG(DemodKargs, name)
+#define DKP(name) LDG_KARG_PTR(DemodKargs, name)
+// The struct is the kernarg segment as the code object lays it out (its .args offsets: every
+// argument at its natural alignment, SysConst at 120, video behind it, span last).
+static_assert(alignof(SysConst) == 8 && offsetof(DemodKargs, fmt) == 48 && offsetof(DemodKargs, tw) == 56 &&
+                  offsetof(DemodKargs, C) == 120 && offsetof(DemodKargs, video) == 120 + sizeof(SysConst) &&
+                  offsetof(DemodKargs, span) == 208 + sizeof(SysConst) && sizeof(DemodKargs) == 216 + sizeof(SysConst),
+              "DemodKargs is the kernels' argument list");
+// The body takes the whole list too (one list, no second order to keep by hand) and names only
+// what the entry uses and tw, twk, rf_filt, iir; naming one of the others there brings its
+// entry load and the spills back (tests/test_kernel_budget.py holds the spill count).
+#define LDG_DEMOD_ARGS LDG_KERNEL_ARGS(LDG_DEMOD_ARG_LIST)
 // PROBE: one workgroup per probe read (slot smap[blockIdx.x], its block 0 only):
 // ldg_k_demod_probe, below.
 template <bool CUT, bool PROBE = false>
@@ -372,7 +387,8 @@ __device__ __forceinline__ void demod_body(LDG_DEMOD_PARAMS) {
   STAMP(0);
   // profiling: the launch's execution span on the constant-rate clock (first
   // workgroup start, last workgroup end), what a kernel trace reports
-  if (span && tid == 0) atomicMax(&span[0], ~(unsigned long long)__builtin_amdgcn_s_memrealtime());
+  if (unsigned long long* const span = DKP(span); span && tid == 0)
+    atomicMax(&span[0], ~(unsigned long long)__builtin_amdgcn_s_memrealtime());
   const int slot = PROBE ? smap[blockIdx.x] : smap[blockIdx.x / MAX_BLOCKS_PER_READ];
   const int b = PROBE ? 0 : blockIdx.x % MAX_BLOCKS_PER_READ;
   const ReadDesc rd = reads[slot];
@@ -383,7 +399,7 @@ __device__ __forceinline__ void demod_body(LDG_DEMOD_PARAMS) {
   const int copylen = (off + (BLOCKLEN - BLOCKCUT) > rd.n_out) ? rd.n_out - off : BLOCKSTEP;
   int64_t rel0 = i0 - cap_first;
   if (rel0 < 0 || rel0 + BLOCKLEN > cap_nsamp) {
-    if (tid == 0) status[slot] = FS_EOF;
+    if (tid == 0) DKP(status)[slot] = FS_EOF;
     return;
   }
   if (ring) {
@@ -394,7 +410,10 @@ __device__ __forceinline__ void demod_body(LDG_DEMOD_PARAMS) {
     cap += (g * bpg) % ring;
     rel0 = i0 - g * spg;
   }
-  double* vout = video + (int64_t)slot * vread_stride + off - BLOCKCUT;   // index by block position p
+  // a channel's output row, indexed by block position p (formed where a phase stores, from that phase's own loads)
+  auto vout = [&](int ch) {
+    return DKP(video) + (int64_t)slot * DK(vread_stride) + off - BLOCKCUT + (int64_t)ch * DK(vchan_stride);
+  };
   const double2* F = rf_filt + (int64_t)rd.filt_slot * BLOCKLEN;
   // odd-half park, in LDS image order (park[u] = the value for LDS slot u), so
   // it returns to LDS by LDS-DMA (global_load_lds) without a register pass.
@@ -459,6 +478,12 @@ __device__ __forceinline__ void demod_body(LDG_DEMOD_PARAMS) {
   const int park_id = uni(s_park);               // the same LDS word for every lane
   const bool park_lost = park_id < 0;
   double2* const park = ospill + (int64_t)(park_lost ? PARK_SCRATCH : park_id) * M;
+  // the block's end: a read that ran on the scratch park is flagged, the span closed
+  auto finish = [&] {
+    if (tid == 0 && park_lost) DKP(status)[slot] = FS_MIGRATED;
+    if (unsigned long long* const span = DKP(span); span && tid == 0)
+      atomicMax(&span[1], (unsigned long long)__builtin_amdgcn_s_memrealtime());
+  };
 
   // ---- 2. analytic-signal spectra and the audio carrier slices ---------------
   // Y = X * RFVideo*MTF^m; the 16384-point IFFT of Y is done as its even/odd
@@ -478,15 +503,15 @@ __device__ __forceinline__ void demod_body(LDG_DEMOD_PARAMS) {
       // bin k = a0 + t into slot j = t; thread t >= 512 the mirrored bin
       // k = a0 + 1 + (t - 512), conjugated, into slot j = a0 + 1024 - k
       const int t = fresh(tid);
-      const int a0 = C.audio_lo0;
+      const int a0 = DK(C).audio_lo0;
       const bool mir = t >= 512;
       const int k = mir ? a0 + 1 + (t - 512) : a0 + t;
       const int j = mir ? a0 + 1024 - k : t;
       double2 xk = rsplit(X_[dr_pos(k)], X_[dr_pos(M - k)], *at32(tw, k));
       if (mir) xk = conj2(xk);
-      const double2 al = cmul(xk, *at32(a_lfilt, j)), ar = cmul(xk, *at32(a_rfilt, j));
+      const double2 al = cmul(xk, *at32(DKP(a_lfilt), j)), ar = cmul(xk, *at32(DKP(a_rfilt), j));
       // per slot (a later call's demod must not overwrite slices ldg_k_audio1 has not read)
-      double2* as = aslice + ((int64_t)slot * MAX_BLOCKS_PER_READ + b) * 2048;   // left [0,1024), right [1024,2048)
+      double2* as = DKP(aslice) + ((int64_t)slot * MAX_BLOCKS_PER_READ + b) * 2048;   // left [0,1024), right [1024,2048)
       *at32(as, j) = al;
       *at32(as + 1024, j) = ar;
     }
@@ -564,7 +589,7 @@ __device__ __forceinline__ void demod_body(LDG_DEMOD_PARAMS) {
   STAMP(8);
   // ---- 5. FM demod (Hz) -> demod spectrum D (parked in ospill) ----------------------------------
   {
-    const double hzk = C.freq_hz / TAU;
+    const double hzk = DK(C).freq_hz / TAU;
     double d0[8], d1[8];
 #pragma unroll
     for (int q = 0; q < 8; q++) {
@@ -599,7 +624,7 @@ __device__ __forceinline__ void demod_body(LDG_DEMOD_PARAMS) {
   double pl1, pt1, p151, p311;
   double2* sx = s_x;                             // chunk layout SWC (iir.hpp) from here on
   {
-    if (!(kProbe & 32)) merge_pairs(X_, twk, g_05, tid, D);
+    if (!(kProbe & 32)) merge_pairs(X_, twk, DKP(g_05), tid, D);
     STAMP(12);
     double2 zr[8];                               // outputs at natural positions t + T q
     fft8k_dit<true, true>(s_x, tw, twl, tid, zr, fl);
@@ -620,7 +645,8 @@ __device__ __forceinline__ void demod_body(LDG_DEMOD_PARAMS) {
     // to [16352, 16384), which is never kept (copylen <= BLOCKSTEP), and that wave's other
     // pairs lie below BLOCKCUT: with lo = -32 it is dropped whole.  The roll makes the waves
     // at both ends of the kept range straddle it; they decide per lane (store_wave).
-    double* o = vout + (int64_t)CH_05 * vchan_stride - BLOCKCUT_END;
+    double* o = vout(CH_05) - BLOCKCUT_END;
+    const double sync_lo = DK(C).sync_lo, sync_hi = DK(C).sync_hi;
     LaneStore ls = lane_store(t);
     ls.wlo -= BLOCKCUT_END;
     const bool st05 = !kProbeNoStore && !(CUT && (int64_t)off >= rd.vcut);
@@ -631,8 +657,8 @@ __device__ __forceinline__ void demod_body(LDG_DEMOD_PARAMS) {
       if (st05) store_q(o, ls, q, make_double2(v0, v1), copylen);
       // detector bits at UNROLLED block positions 2m, 2m + 1; lanes 8j..8j+7 (pairs
       // of 16 consecutive samples) OR their bits into lane 8j+7 (DPP row shifts)
-      const uint32_t f0 = (v0 >= C.sync_lo && v0 <= C.sync_hi) ? 1u : 0u;
-      const uint32_t f1 = (v1 >= C.sync_lo && v1 <= C.sync_hi) ? 1u : 0u;
+      const uint32_t f0 = (v0 >= sync_lo && v0 <= sync_hi) ? 1u : 0u;
+      const uint32_t f1 = (v1 >= sync_lo && v1 <= sync_hi) ? 1u : 0u;
       int xb = (int)((f0 | (f1 << 1)) << (2 * (t & 7)));
       xb |= __builtin_amdgcn_mov_dpp(xb, 0x111, 0xf, 0xf, true);   // row_shr:1
       xb |= __builtin_amdgcn_mov_dpp(xb, 0x112, 0xf, 0xf, true);   // row_shr:2
@@ -654,8 +680,8 @@ __device__ __forceinline__ void demod_body(LDG_DEMOD_PARAMS) {
     // (chunk t of the block is chunk cbase + t of the slot: a wave-uniform base, a 32-bit lane part)
     const int64_t cbase = (int64_t)slot * CHUNKS_PER_SLOT + (off >> 4) - BLOCKCUT / 16;
     if (16 * t >= BLOCKCUT && 16 * t < BLOCKCUT + copylen) {
-      *at32(sst + cbase, t) = st_in;
-      *at32(sbits + cbase, t) = cur | (prv << 16);
+      *at32(DKP(sst) + cbase, t) = st_in;
+      *at32(DKP(sbits) + cbase, t) = cur | (prv << 16);
     }
     // sync tiles (common.hpp SyncTile): tile j = outputs [off + 32 j, +32) =
     // block positions [1024 + 32 j, +32) = chunks of threads 64 + 2 j (+1); np.argmax
@@ -683,7 +709,7 @@ __device__ __forceinline__ void demod_body(LDG_DEMOD_PARAMS) {
         tt.v = v;
         tt.idx = vi == 0x7fffffff ? 0x7fffffffffffffffLL : (int64_t)off + vi;
         // tile (off >> 5) + j of the slot, j = (t >> 1) - 32
-        *at32(stiles + ((int64_t)slot * STILE_PER_SLOT + (off >> 5) - 32), t >> 1) = tt;
+        *at32(DKP(stiles) + ((int64_t)slot * STILE_PER_SLOT + (off >> 5) - 32), t >> 1) = tt;
       }
     }
   }
@@ -691,13 +717,12 @@ __device__ __forceinline__ void demod_body(LDG_DEMOD_PARAMS) {
   // past the read's video cut nothing reads the video, burst or pilot channel (the
   // field kernels check, FS_VCUT): the block ends after the sync channel
   if (CUT && (int64_t)off >= rd.vcut) {
-    if (tid == 0 && park_lost) status[slot] = FS_MIGRATED;
-    if (span && tid == 0) atomicMax(&span[1], (unsigned long long)__builtin_amdgcn_s_memrealtime());
+    finish();
     return;
   }
   double4 mlb, mtb, m15b, m31b;
   {
-    if (!(kProbe & 32)) merge_pairs(X_, twk, g_video, tid, D);
+    if (!(kProbe & 32)) merge_pairs(X_, twk, DKP(g_video), tid, D);
     STAMP(16);
     double2 zr[8];
     if (!(kProbe & 2)) fft8k_dit<true, true>(s_x, tw, twl, tid, zr, fl);
@@ -708,7 +733,7 @@ __device__ __forceinline__ void demod_body(LDG_DEMOD_PARAMS) {
     mtb = iir2_pow(iir + IIR_MB, t);
     m15b = iir2_pow(iir + IIR_MB, scan_d15(t & 63));
     m31b = iir2_pow(iir + IIR_MB, scan_d31(t & 63));
-    double* o = vout + (int64_t)CH_DEMOD * vchan_stride;
+    double* o = vout(CH_DEMOD);
     const LaneStore ls = lane_store(t);
 #pragma unroll
     for (int q = 0; q < 8; q++) {
@@ -736,9 +761,9 @@ __device__ __forceinline__ void demod_body(LDG_DEMOD_PARAMS) {
     // the compact burst channel (chan.hpp): the kept chunks' entering states
     if (16 * t >= BLOCKCUT && 16 * t < BLOCKCUT + copylen) {
       const int64_t cbase = (int64_t)slot * CHUNKS_PER_SLOT + (off >> 4) - BLOCKCUT / 16;
-      *at32(bst + cbase, t) = make_double4(s_in.x, s_in.y, h.y, h.x);
+      *at32(DKP(bst) + cbase, t) = make_double4(s_in.x, s_in.y, h.y, h.x);
     }
-    if (C.n_chan > 4) {
+    if (DK(C).n_chan > 4) {
       // PAL pilot from the same demod samples (still in x); iir2's barriers order
       // every thread's reads of sx above before the writes below
       double2 p_in;
@@ -747,12 +772,11 @@ __device__ __forceinline__ void demod_body(LDG_DEMOD_PARAMS) {
 #pragma unroll
       for (int c = 0; c < 8; c++) sx[SWC(8 * t + c)] = make_double2(y[2 * c], y[2 * c + 1]);
       __syncthreads();
-      store_chan(sx, vout + (int64_t)CH_PILOT * vchan_stride, t, copylen);
+      store_chan(sx, vout(CH_PILOT), t, copylen);
     }
   }
   STAMP(19);
-  if (tid == 0 && park_lost) status[slot] = FS_MIGRATED;
-  if (span && tid == 0) atomicMax(&span[1], (unsigned long long)__builtin_amdgcn_s_memrealtime());
+  finish();
 }
 
 extern "C" __global__ __launch_bounds__(1024) void ldg_k_demod(LDG_DEMOD_PARAMS) { demod_body<true>(LDG_DEMOD_ARGS); }

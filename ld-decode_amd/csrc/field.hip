@@ -47,51 +47,65 @@ struct SyncView {
 // First-occurrence argmax of ds[i, wend) with numpy semantics (a NaN is the
 // maximum; the first NaN wins), one wave: 20 coalesced loads per lane issued
 // back to back, then a cross-lane reduction.  Window <= 1280 samples.
+// Positions in a read are below MAX_NOUT, so the candidates' indices are carried as
+// unsigned 32-bit words (half the registers, shuffles and compares of int64_t ones; the
+// order of two indices, and so every tie, is the same).  AM_NONE, "no candidate", is the
+// largest: it loses every comparison, and it is what SyncTile::idx's INT64_MAX truncates to.
 constexpr int ARGMAX_PER = 20;
+constexpr uint32_t AM_NONE = 0xffffffffu;
+static_assert(MAX_NOUT < 0x7fffffff && (uint32_t)0x7fffffffffffffffLL == AM_NONE, "32-bit read positions");
+// (v, vi) comes before (b, bi) in np.argmax order (am_beats, common.hpp)
+__device__ __forceinline__ bool am_beats_u32(double v, uint32_t vi, double b, uint32_t bi) {
+  const bool vn = v != v, bn = b != b;
+  if (vn || bn) return vn && (!bn || vi < bi);
+  return v > b || (v == b && vi < bi);
+}
 template <class Src>
-__device__ inline void wave_argmax(const Src& ds, int64_t i, int64_t wend, int lane, double& best,
-                                   int64_t& bidx) {
+__device__ inline void wave_argmax(const Src& ds, int i, int wend, int lane, double& best, uint32_t& bidx) {
   double vv[ARGMAX_PER];
 #pragma unroll
   for (int q = 0; q < ARGMAX_PER; q++) {
-    const int64_t k = i + lane + 64 * q;
+    const int k = i + lane + 64 * q;
     vv[q] = (k < wend) ? ds[k] : -__builtin_inf();
   }
   best = -__builtin_inf();
-  bidx = 0x7fffffffffffffffLL;
+  bidx = AM_NONE;
 #pragma unroll
-  for (int q = 0; q < ARGMAX_PER; q++)
-    if (am_beats(vv[q], i + lane + 64 * q, best, bidx)) { best = vv[q]; bidx = i + lane + 64 * q; }
+  for (int q = 0; q < ARGMAX_PER; q++) {
+    const uint32_t k = (uint32_t)(i + lane + 64 * q);
+    if (am_beats_u32(vv[q], k, best, bidx)) { best = vv[q]; bidx = k; }
+  }
   for (int o = 32; o > 0; o >>= 1) {
     const double ov = __shfl_xor(best, o);
-    const int64_t oi = __shfl_xor(bidx, o);
-    if (am_beats(ov, oi, best, bidx)) { best = ov; bidx = oi; }
+    const uint32_t oi = __shfl_xor(bidx, o);
+    if (am_beats_u32(ov, oi, best, bidx)) { best = ov; bidx = oi; }
   }
 }
 
 // wave_argmax from the sync tiles: whole tiles inside [i, wend) plus the raw
 // samples of the two ragged ends (one load per lane each instead of 20).
 template <class Src>
-__device__ inline void tile_argmax(const Src& ds, const SyncTile* __restrict__ tiles, int64_t i,
-                                   int64_t wend, int lane, double& best, int64_t& bidx) {
-  const int64_t t0 = (i + 31) >> 5, t1 = wend >> 5;         // whole tiles [t0, t1)
+__device__ inline void tile_argmax(const Src& ds, const SyncTile* __restrict__ tiles, int i, int wend, int lane,
+                                   double& best, uint32_t& bidx) {
+  const int t0 = (i + 31) >> 5, t1 = wend >> 5;             // whole tiles [t0, t1)
   if (t0 >= t1) { wave_argmax(ds, i, wend, lane, best, bidx); return; }
-  const int64_t h1 = t0 << 5, s1 = t1 << 5;               // raw [i, h1) and [s1, wend), < 32 each
+  const int h1 = t0 << 5, s1 = t1 << 5;                   // raw [i, h1) and [s1, wend), < 32 each
   double v = -__builtin_inf();
-  int64_t vi = 0x7fffffffffffffffLL;
+  uint32_t vi = AM_NONE;
   {
-    const int64_t k = (lane < 32) ? i + lane : s1 + (lane - 32);
+    const int k = (lane < 32) ? i + lane : s1 + (lane - 32);
     const bool in = (lane < 32) ? (k < h1) : (k < wend);
-    if (in) { v = ds[k]; vi = k; }
+    if (in) { v = ds[k]; vi = (uint32_t)k; }
   }
-  for (int64_t t = t0 + lane; t < t1; t += 64) {
+  for (int t = t0 + lane; t < t1; t += 64) {
     const SyncTile T = tiles[t];
-    if (am_beats(T.v, T.idx, v, vi)) { v = T.v; vi = T.idx; }
+    const uint32_t ti = (uint32_t)T.idx;                  // a tile with no output: INT64_MAX -> AM_NONE
+    if (am_beats_u32(T.v, ti, v, vi)) { v = T.v; vi = ti; }
   }
   for (int o = 32; o > 0; o >>= 1) {
     const double ov = __shfl_xor(v, o);
-    const int64_t oi = __shfl_xor(vi, o);
-    if (am_beats(ov, oi, v, vi)) { v = ov; vi = oi; }
+    const uint32_t oi = __shfl_xor(vi, o);
+    if (am_beats_u32(ov, oi, v, vi)) { v = ov; vi = oi; }
   }
   best = v;
   bidx = vi;
@@ -151,21 +165,23 @@ extern "C" __global__ __launch_bounds__(64) void ldg_k_sync_walk(
   const WalkGeom G(rd.n_out, C.linelen);
   const SyncSrc ds(sst, sbits, slot, C);
   const SyncTile* tl = stiles + (int64_t)slot * STILE_PER_SLOT;
-  int64_t i = (int64_t)k * G.seg;
-  int64_t e = (k == SEG_K - 1) ? G.stop : (int64_t)(k + 1) * G.seg + G.ov;
-  if (e > G.stop) e = G.stop;
+  // (read positions: 32-bit, wave_argmax)
+  int i = (int)((int64_t)k * G.seg);
+  int64_t e64 = (k == SEG_K - 1) ? G.stop : (int64_t)(k + 1) * G.seg + G.ov;
+  if (e64 > G.stop) e64 = G.stop;
+  const int e = (int)e64;
   int n = 0;
   int32_t* P = node_pos + L * SEG_NMAX;
   int32_t* K = node_pk + L * SEG_NMAX;
   double* V = node_lv + L * SEG_NMAX;
   while (i < e && n < SEG_NMAX) {
     double best;
-    int64_t bidx;
+    uint32_t bidx;
     tile_argmax(ds, tl, i, i + G.win, lane, best, bidx);
     const bool pk = best > .2;
-    if (lane == 0) { P[n] = (int32_t)i; K[n] = pk ? (int32_t)bidx : -1; V[n] = best; }
+    if (lane == 0) { P[n] = i; K[n] = pk ? (int32_t)bidx : -1; V[n] = best; }
     n++;
-    i = pk ? bidx + G.jump : i + G.win;
+    i = pk ? (int)bidx + G.jump : i + G.win;
   }
   if (lane == 0) node_n[L] = n;
 }
@@ -351,13 +367,13 @@ extern "C" __global__ __launch_bounds__(64) void ldg_k_sync(
         }
         if (joined) break;
         double best;
-        int64_t bidx;
-        tile_argmax(ds, stiles + (int64_t)slot * STILE_PER_SLOT, p, p + G.win, lane, best, bidx);
+        uint32_t bidx;
+        tile_argmax(ds, stiles + (int64_t)slot * STILE_PER_SLOT, (int)p, (int)p + G.win, lane, best, bidx);
         if (best > .2) {
           if (np >= MAX_PEAKS) { overflow = true; break; }
           if (lane == 0) { s_pk[np] = (int32_t)bidx; s_lv[np] = best; s_lvi[np] = -1; }
           np++;
-          p = bidx + G.jump;
+          p = (int64_t)bidx + G.jump;
         } else {
           p += G.win;
         }
@@ -776,7 +792,10 @@ __device__ void hsync_line(const Src& d05, int64_t len, const SysConst& C, int i
 }
 }  // namespace
 
-extern "C" __global__ __launch_bounds__(64) void ldg_k_hsync_lines(
+// (8 waves per SIMD asked for: the register allocator, left alone, took 100 VGPRs -- 4 waves -- for
+// the same instructions; asked, it takes 52 with no scratch and not one instruction more.  The
+// kernel waits on memory, so the waves it keeps resident are what its CU time goes by.)
+extern "C" __global__ __launch_bounds__(64, 8) void ldg_k_hsync_lines(
     const int32_t* __restrict__ smap, const double* __restrict__ video, int64_t vread_stride, int64_t vchan_stride,
     SysConst C, FieldRec* __restrict__ recs, double* __restrict__ lines, int8_t* __restrict__ bad,
     const ReadDesc* __restrict__ reads) {
