@@ -738,6 +738,62 @@ int ldg_cx_create(ldg_cx** out);
 int ldg_cx_destroy(ldg_cx* cx);
 int ldg_cx_process(ldg_cx* cx, int64_t n, const uint16_t* in, uint16_t* out);
 
+/* ---- FLAC-compressed captures: .ldf, .flac, .oga (build-defined) ----------
+ * The bit stream is the public FLAC format (RFC 9639), native or in Ogg, one channel of 16-bit
+ * (-> LDG_FMT_S16) or 8-bit (sample + 128 -> LDG_FMT_U8) samples; what is done with a damaged file
+ * is this project's rule R0-R6, restated in tests/flac_ref.py, which the device equals exactly.
+ * One file is open on a context at a time.
+ *   ldg_flac_open     maps the file, reads the container and STREAMINFO (host only).  LDG_EINVAL with
+ *                     the reason in ldg_last_error for a file this project does not read.
+ *   ldg_flac_index    finds, walks and keeps every frame of the file on the device, chunk_bytes of it
+ *                     a launch (0: 64 MiB; rounded up so that a chunk and its carry hold the largest
+ *                     frame), and fills `out`.  The result does not depend on chunk_bytes.
+ *   ldg_flac_frames   copies the accepted frames (byte order) and the gaps ((first, count) pairs) out:
+ *                     at most cap_frames / cap_gaps of them (counters.frames / .gaps say how many).
+ *   ldg_flac_read     decodes samples [first_sample, first_sample + nsamples) (within [0, nsamples of
+ *                     the index)) into dst, host or device memory, in the stream's LDG_FMT_*; samples
+ *                     no kept frame covers are 0 (128 as u8).
+ *   ldg_flac_capture  the same into a buffer the library owns, which becomes the resident capture as
+ *                     after ldg_set_capture(ctx, buf, nsamples, fmt, first_sample, 1).
+ *   ldg_flac_close    forgets the file (the resident capture stays).
+ * ldg_flac_index, _read and _capture work on a stream of their own and return after it is idle: what
+ * they wrote (a device dst included) is complete on return, and a device dst must not be in use by
+ * the caller's own streams during the call.  The file stays mapped while it is open: it must not be
+ * truncated meanwhile (that is a bus error, not an LDG_E*); a file whose bytes changed in place is
+ * caught by ldg_flac_read (LDG_ESTATE). */
+#define LDG_FLAC_NATIVE 0
+#define LDG_FLAC_OGG 1
+#define LDG_FLAC_KEPT 0      /* placed in the output                                            */
+#define LDG_FLAC_NESTED 1    /* begins inside the frame kept before it                          */
+#define LDG_FLAC_MISPLACED 2 /* its position lies below the end of the frame kept before it     */
+#define LDG_FLAC_INFO_SIZE 72
+typedef struct ldg_flac_info {
+  int32_t container;  /* LDG_FLAC_NATIVE / LDG_FLAC_OGG */
+  int32_t fmt;        /* LDG_FMT_S16 or LDG_FMT_U8 of the decoded samples */
+  int32_t bps, channels, sample_rate, min_block, max_block, pad_;
+  int64_t total_samples; /* as STREAMINFO states it: often 0, reported and never trusted */
+  int64_t file_bytes, audio_offset;
+  uint8_t md5[16];       /* of the signed samples, as STREAMINFO states it (all 0: none) */
+} ldg_flac_info;
+#define LDG_FLAC_COUNTERS_SIZE 112
+typedef struct ldg_flac_counters {
+  int64_t candidates, header_ok, parsed, accepted, kept, nested, misplaced, range, ogg_broken, lost_bytes, gaps,
+      gap_samples;
+  int64_t nsamples; /* N: the largest end of a kept frame */
+  int64_t frames;   /* entries of the frame table (the accepted frames) */
+} ldg_flac_counters;
+#define LDG_FLAC_FRAME_SIZE 32
+typedef struct ldg_flac_frame {
+  int64_t offset, bytes, position; /* file offset of its first byte; its length; its first sample */
+  int32_t block_size, state;       /* LDG_FLAC_KEPT ... */
+} ldg_flac_frame;
+int ldg_flac_open(ldg_ctx* ctx, const char* path, ldg_flac_info* info);
+int ldg_flac_index(ldg_ctx* ctx, int64_t chunk_bytes, ldg_flac_counters* out);
+int ldg_flac_frames(ldg_ctx* ctx, ldg_flac_frame* frames, int64_t cap_frames, int64_t* gaps, int64_t cap_gaps);
+int ldg_flac_read(ldg_ctx* ctx, int64_t first_sample, int64_t nsamples, void* dst, int dst_is_device);
+int ldg_flac_capture(ldg_ctx* ctx, int64_t first_sample, int64_t nsamples);
+int ldg_flac_close(ldg_ctx* ctx);
+
 /* Library / device identification. */
 const char* ldg_version(void);
 int ldg_device_count(void);

@@ -55,6 +55,7 @@ struct ldg_efm_state;             // efm.inc: the EFM run-length extraction's op
 struct ldg_efmdec_state;          // efmdec.inc: the EFM decode's table, carried stream and buffers
 struct ldg_efmsec_state;          // efmsec.inc: the EFM data sectors' tables, carried bytes and buffers
 struct ldg_lines_state;           // lines.inc: the NTSC line services' buffers
+struct ldg_flac_state;            // flac.inc: an open FLAC-compressed capture, its index and staging
 
 struct ldg_ctx {
   int device = 0;
@@ -235,6 +236,7 @@ struct ldg_ctx {
   ldg_efmdec_state* efmdec = nullptr;   // EFM decode (efmdec.hip), allocated by ldg_efmdec_set_table
   ldg_efmsec_state* efmsec = nullptr;   // EFM data sectors (efmsec.hip), allocated on first use
   ldg_lines_state* lines = nullptr;     // NTSC line services (lines.hip), allocated on first use
+  ldg_flac_state* flac = nullptr;       // FLAC-compressed capture (flac.hip), allocated by ldg_flac_open
   hipEvent_t ev_fbuf[2] = {nullptr, nullptr};
   bool fbuf_recorded[2] = {false, false};
   hipEvent_t ev_tbc = nullptr;
@@ -695,6 +697,7 @@ static void efm_free(ldg_ctx* ctx);   // efm.inc
 static void efmdec_free(ldg_ctx* ctx);   // efmdec.inc
 static void efmsec_free(ldg_ctx* ctx);   // efmsec.inc
 static void lines_free(ldg_ctx* ctx);    // lines.inc
+static void flac_free(ldg_ctx* ctx);     // flac.inc
 
 int ldg_destroy(ldg_ctx* ctx) {
   if (!ctx) return LDG_EINVAL;
@@ -744,6 +747,7 @@ int ldg_destroy(ldg_ctx* ctx) {
   efmdec_free(ctx);
   efmsec_free(ctx);
   lines_free(ctx);
+  flac_free(ctx);
   if (ctx->cap_owned) dfree(ctx->cap);
 
   for (void* p : {(void*)ctx->comb_state, (void*)ctx->comb_abl, (void*)ctx->comb_in, (void*)ctx->comb_rgb,

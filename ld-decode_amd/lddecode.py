@@ -29,8 +29,10 @@ sys.path.insert(0, HERE)
 
 import numpy as np  # noqa: E402
 
+from ldgpu import native  # noqa: E402
 from ldgpu.decoder import GPUDecoder  # noqa: E402
-from ldgpu.formats import fmt_from_path, read_samples, samples_in_bytes  # noqa: E402
+from ldgpu.flac import FlacFile, is_flac_path  # noqa: E402
+from ldgpu.formats import bytes_for_samples, fmt_from_path, read_samples, samples_in_bytes  # noqa: E402
 
 
 class Writer:
@@ -181,6 +183,13 @@ def main(argv=None):
         print("ERROR: --efm is a second pass of one plain decode: not with sharding (WORLD_SIZE > 1), "
               "--epoch-frames / --manifest or -c; run efm_extract.py on the capture instead")
         return 1
+    # a FLAC-compressed capture (.ldf, .flac, .oga) is decoded to its samples on the GPU and then
+    # behaves as the .r16 (or .u8) of those samples; what reads the raw file itself is refused
+    flac = is_flac_path(filename)
+    if flac and (world > 1 or args.epoch_frames or args.manifest or args.efm):
+        print("ERROR: a FLAC-compressed capture (%s) decodes in one piece: not with sharding (WORLD_SIZE > 1), "
+              "--epoch-frames / --manifest or --efm*; unpack it with ldf_unpack.py first" % filename)
+        return 1
     rccl = False
     if world > 1:
         # one process per GPU (python -m torch.distributed.run --nproc-per-node N lddecode.py ...):
@@ -235,14 +244,41 @@ def main(argv=None):
         dec.ctx.comb_set_opts(opticalflow=True)
     samples_per_frame = dec.rf.samples_per_frame                 # int(fs / FPS) + 1
     bytes_per_frame = samples_per_frame * 5 // 4                 # for 10-bit packed files
-    infile_size = os.path.getsize(filename)
+    flac_in = None
+    if flac:
+        try:
+            flac_in = FlacFile(dec.ctx, filename)
+        except native.LDGError as e:
+            print('ERROR: %s' % e)
+            return 1
+        c = flac_in.counters
+        print('flac: %d samples in %d frames (%d bytes lost, %d gaps of %d samples)' % (
+            flac_in.nsamples, c['kept'], c['lost_bytes'], c['gaps'], c['gap_samples']))
+        infile_size = bytes_for_samples(flac_in.fmt, flac_in.nsamples)     # of the .r16 / .u8 it stands for
+    else:
+        infile_size = os.path.getsize(filename)
     if (infile_size // bytes_per_frame - firstframe) < 2:
         print('Error: start frame is past end of file')
         return 1
 
-    fmt = fmt_from_path(filename)
-    raw = np.memmap(filename, dtype=np.uint8, mode='r')
-    if world == 1 and args.window_mb > 0:
+    if not flac:
+        fmt = fmt_from_path(filename)
+        raw = np.memmap(filename, dtype=np.uint8, mode='r')
+    if flac:
+        fmt, raw = flac_in.fmt, None
+        if args.window_mb != 2048:
+            print('note: --window-mb is ignored for a FLAC-compressed capture (its samples are resident)')
+        # the whole capture becomes resident: 2 bytes (or 1) a sample, next to the decode's own scratch
+        # and staging (256 MiB + 64 MiB, csrc/flac.inc)
+        free, _ = native.device_memory(args.device)
+        if infile_size + (512 << 20) > free:
+            print('ERROR: the %d samples of %s need %.1f GB of device memory and %.1f GB are free: unpack it with '
+                  'ldf_unpack.py (--start-sample / --length for a part) and decode the .r16 with -s / -l, which '
+                  'streams from storage' % (flac_in.nsamples, filename, infile_size / 1e9, free / 1e9))
+            return 1
+        flac_in.capture(0, flac_in.nsamples)
+        dec.use_resident_capture(fmt, flac_in.nsamples)
+    elif world == 1 and args.window_mb > 0:
         # streamed from storage through an HBM ring, the read overlapped with the decode
         dec.open_stream(filename, fmt, args.window_mb << 20, first_sample=firstframe * dec.rf.samples_per_frame)
     elif world == 1 or args.seek >= 0 or args.cut:
@@ -261,9 +297,11 @@ def main(argv=None):
         lastsample += int(samples_per_frame * .25)
         total = samples_in_bytes(fmt, infile_size)
         with open(outname + '.r16', 'wb') as out:
-            for i in range(nextsample, lastsample, 16384):
-                n = min(16384, lastsample - i, max(0, total - i))
-                out.write(read_samples(raw, fmt, i, n).astype(np.int16).tobytes())
+            step = 1 << 22 if flac else 16384
+            for i in range(nextsample, lastsample, step):
+                n = min(step, lastsample - i, max(0, total - i))
+                piece = flac_in.read(i, n) if flac else read_samples(raw, fmt, i, n)
+                out.write(piece.astype(np.int16).tobytes())
         return 0
 
     num_frames = req_frames if req_frames is not None else infile_size // bytes_per_frame - firstframe

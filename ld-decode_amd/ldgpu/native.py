@@ -35,7 +35,8 @@ EXPORTS = ['ldg_create', 'ldg_destroy', 'ldg_last_error', 'ldg_set_filters', 'ld
            'ldg_efm_defaults', 'ldg_efm_set_opts', 'ldg_efm_window', 'ldg_efm_extract', 'ldg_efm_debug_read',
            'ldg_efmdec_set_table', 'ldg_efmdec_reset', 'ldg_efmdec_feed', 'ldg_efmdec_read',
            'ldg_efmsec_enable', 'ldg_efmsec_reset', 'ldg_efmsec_feed', 'ldg_efmsec_last_info', 'ldg_efmsec_read',
-           'ldg_field_line_services', 'ldg_frames_line_services']
+           'ldg_field_line_services', 'ldg_frames_line_services',
+           'ldg_flac_open', 'ldg_flac_index', 'ldg_flac_frames', 'ldg_flac_read', 'ldg_flac_capture', 'ldg_flac_close']
 STACK_MAX_SOURCES = 16            # LDG_STACK_MAX_SOURCES
 STACK_MODES = {'median': 0, 'mean': 1, 'smart-mean': 2}      # LDG_STACK_*
 STACK_STATS = ('h2d_s', 'kernel_s', 'd2h_s', 'calls')        # ldg_stack_stats, in order
@@ -128,6 +129,30 @@ def line_services_json(d):
             'cc': [d['cc'][0], d['cc'][1]] if d['cc_state'] != LINE_ABSENT else None, 'ccState': d['cc_state'],
             'videoId': d['vid_bits'] >> 6 if d['vid_state'] == LINE_OK else None,
             'videoIdBits': d['vid_bits'], 'videoIdState': d['vid_state']}
+
+
+class FlacInfo(C.Structure):
+    """ldg_flac_info: the container and STREAMINFO of an open FLAC-compressed capture."""
+    _fields_ = [('container', C.c_int32), ('fmt', C.c_int32), ('bps', C.c_int32), ('channels', C.c_int32),
+                ('sample_rate', C.c_int32), ('min_block', C.c_int32), ('max_block', C.c_int32), ('pad_', C.c_int32),
+                ('total_samples', C.c_int64), ('file_bytes', C.c_int64), ('audio_offset', C.c_int64),
+                ('md5', C.c_uint8 * 16)]
+
+
+FLAC_COUNTERS = ('candidates', 'header_ok', 'parsed', 'accepted', 'kept', 'nested', 'misplaced', 'range',
+                 'ogg_broken', 'lost_bytes', 'gaps', 'gap_samples')
+
+
+class FlacCounters(C.Structure):
+    """ldg_flac_counters: what ldg_flac_index found."""
+    _fields_ = [(k, C.c_int64) for k in FLAC_COUNTERS + ('nsamples', 'frames')]
+
+
+# ldg_flac_frame
+FLAC_FRAME = np.dtype([('offset', '<i8'), ('bytes', '<i8'), ('position', '<i8'), ('block_size', '<i4'),
+                       ('state', '<i4')])
+FLAC_INFO_SIZE, FLAC_COUNTERS_SIZE, FLAC_FRAME_SIZE = 72, 112, 32      # LDG_FLAC_*_SIZE
+FLAC_KEPT, FLAC_NESTED, FLAC_MISPLACED = range(3)                      # LDG_FLAC_*
 
 
 class EfmOpts(C.Structure):
@@ -318,6 +343,12 @@ def load(path=None):
     lib.ldg_efmsec_read.restype = C.c_int64
     lib.ldg_field_line_services.argtypes = [vp, C.c_int, vp, vp]
     lib.ldg_frames_line_services.argtypes = [vp, C.c_int, vp, C.c_int, vp]
+    lib.ldg_flac_open.argtypes = [vp, C.c_char_p, C.POINTER(FlacInfo)]
+    lib.ldg_flac_index.argtypes = [vp, C.c_int64, C.POINTER(FlacCounters)]
+    lib.ldg_flac_frames.argtypes = [vp, vp, C.c_int64, vp, C.c_int64]
+    lib.ldg_flac_read.argtypes = [vp, C.c_int64, C.c_int64, vp, C.c_int]
+    lib.ldg_flac_capture.argtypes = [vp, C.c_int64, C.c_int64]
+    lib.ldg_flac_close.argtypes = [vp]
     lib.ldg_version.restype = C.c_char_p
     lib.ldg_device_count.restype = C.c_int
     _lib = lib
